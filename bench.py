@@ -28,9 +28,16 @@ r % device_count, as ref/launch_dist.py:47 binds devices).
 
 The gradient all-reduce runs at every N, including N=1 (a one-rank communicator, exactly what
 upstream DDP does), so every point of the scaling curve executes the same code path;
-``--no-force-comm`` skips it at N=1.  After the timed region (never inside it) the bench measures
-per-bucket device-timed collective durations over a few eager steps and the step time of a
-comm-free graph; their difference to the timed step is the exposed (non-overlapped) comm time.
+``--no-force-comm`` skips it at N=1.
+
+A plain run sets up, warms up, times ``--steps`` steps, writes ``--dump-outputs DIR`` if asked and prints
+the result line.  ``--full`` adds the comm-statistics phase after the timed region (never inside it):
+per-bucket device-timed collective durations over a few eager steps and the step time of a comm-free
+graph; their difference to the timed step is the exposed (non-overlapped) comm time.
+
+``--dump-outputs DIR`` writes what the last timed step computed (loss, updated parameters, gradients)
+as ``DIR/<name>.npy``; the timed steps then start from the seeded initial state, so two builds can be
+compared output for output.
 
 ``--cpu`` runs the same flow on CPU ranks over the native host-ring ("gloo") backend and the ATen
 ConvNet: a plumbing rehearsal (BASELINE config #1), not a GPU measurement.
@@ -99,9 +106,18 @@ def parse(argv=None):
                                                                      "comm_tuning.json"),
                     help="settings from tools/comm_bench.py --recommend, adopted when measured at this world size "
                          "(environment variables already set win)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the comm-statistics phase (see --comm-stats-steps); "
+                         "a plain run only sets up, warms up, times --steps steps and prints the result line")
     ap.add_argument("--comm-stats-steps", type=int, default=20,
-                    help="after the timed region: eager steps with device-timed bucket collectives and "
-                         "comm-free graph replays for the exposed-comm estimate (0 = skip)")
+                    help="with --full, after the timed region: eager steps with device-timed bucket collectives "
+                         "and comm-free graph replays for the exposed-comm estimate (0 = skip)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy "
+                         "(float32): loss, every parameter / buffer after its update and every gradient; at most "
+                         "64 MB in all (larger models: a fixed seeded sample of each array).  The model and "
+                         "optimizer state are put back to their seeded initial values before the first timed "
+                         "step, so the dump depends on the arguments only, not on how many warmup steps ran")
     ap.add_argument("--cpu", action="store_true",
                     help="CPU ranks on the host-ring ('gloo') backend with the ATen ConvNet (plumbing only)")
     ap.add_argument("--local-rank", "--local_rank", type=int, default=None)
@@ -161,6 +177,52 @@ def _pack_batch(x: torch.Tensor, y: torch.Tensor):
     xv.copy_(x)
     yv.copy_(y)
     return buf, xv, yv
+
+
+def _restore_initial(model, opt, initial: dict) -> None:
+    """--dump-outputs: parameters, buffers and momentum as they were before the first step, so the timed
+    steps start from the seeded state however many warmup steps ran (their count follows the clock)."""
+    from ringdp.ops.convnet import pack_states
+
+    with torch.no_grad():
+        for k, v in model.state_dict().items():
+            v.copy_(initial[k])
+        for st in opt.state.values():
+            # zeroed momentum gives the first step's buf = grad (dampening is 0 in every config here)
+            if st.get("momentum_buffer") is not None:
+                st["momentum_buffer"].zero_()
+    for st in pack_states():  # the ConvNet's bf16 weight fragments: rebuilt here, not in the first timed step
+        if st.stale():
+            st.repack()
+
+
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000  # all of --dump-outputs stays below 64 MB
+
+
+def _dump_outputs(path: str, loss, model) -> None:
+    """What a caller of the timed step holds after the last one: its loss, the updated parameters / buffers
+    and the gradients.  Floating tensors as float32, integer ones as float64.  Above DUMP_LIMIT_BYTES every
+    array is cut to the same fraction of its elements, at sorted flat indices drawn without replacement
+    from a generator seeded by the array's position: the same elements in every run."""
+    import numpy as np
+
+    arrays = [("loss", loss.detach())] if loss is not None else []
+    arrays += [(f"param.{k}", v.detach()) for k, v in model.state_dict().items()]
+    arrays += [(f"grad.{k}", p.grad.detach()) for k, p in model.named_parameters() if p.grad is not None]
+    size = lambda t: t.numel() * (4 if t.is_floating_point() else 8)  # noqa: E731
+    total = sum(size(t) for _, t in arrays)
+    keep = min(1.0, DUMP_LIMIT_BYTES / max(total, 1))
+    os.makedirs(path, exist_ok=True)
+    for i, (name, t) in enumerate(arrays):
+        flat = t.reshape(-1)
+        if keep < 1.0 and flat.numel() > 1:
+            k = max(1, int(flat.numel() * keep))
+            idx = np.sort(np.random.default_rng(i).choice(flat.numel(), size=k, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        else:
+            flat = flat.reshape(t.shape)
+        a = flat.to(torch.float32 if t.is_floating_point() else torch.float64).cpu().numpy()
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def _phase(msg: str) -> None:
@@ -236,6 +298,8 @@ def worker(args):
         if args.dtype == "fp32":
             raise SystemExit("--dtype fp32 is implemented for --model convnet")
         model = getattr(models, args.model)(num_classes=NUM_CLASSES[args.model]).to(dev)
+    # --dump-outputs: the seeded initial state, put back before the first timed step (_restore_initial)
+    initial = {k: v.detach().clone() for k, v in model.state_dict().items()} if args.dump_outputs else None
     ddp = DDP(model, device_ids=[dev.index] if on_gpu else None, output_device=dev.index if on_gpu else None,
               bucket_cap_mb=args.bucket_mb, first_bucket_mb=args.first_bucket_mb)
     if args.comm_hook != "allreduce":
@@ -402,9 +466,13 @@ def worker(args):
     if extra:
         run_steps(extra, graph)
     n_warm += extra
+    if initial is not None:
+        _restore_initial(model, opt, initial)
     _phase(f"timed region: {args.steps} steps")
     elapsed_max, loss = timed(args.steps, graph)
     final_loss = float(loss.item()) if loss is not None else float("nan")
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, loss, model)
     ms_per_step = 1000.0 * elapsed_max / args.steps
     value = world * B * args.steps / elapsed_max
     if rank == 0 and elapsed_max < 1.0:
@@ -484,6 +552,12 @@ def worker(args):
             if text_only:
                 return json.dumps(res)
             print(json.dumps(res), flush=True)
+
+    if not args.full:
+        # a plain run ends here: the comm-statistics phase takes runs of its own
+        emit(comm_stats)
+        dist.destroy_process_group()
+        return
 
     # The headline number is already measured: should the comm-statistics phase below stop making
     # progress, a native timer writes the result line without those statistics and ends the rank

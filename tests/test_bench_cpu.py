@@ -13,7 +13,8 @@ from conftest import ROOT, free_port
 
 pytestmark = pytest.mark.slow
 
-ARGS = ["--cpu", "--steps", "2", "--warmup", "1", "--batch-per-rank", "8", "--comm-stats-steps", "1"]
+PLAIN = ["--cpu", "--steps", "2", "--warmup", "1", "--batch-per-rank", "8"]
+ARGS = PLAIN + ["--full", "--comm-stats-steps", "1"]
 
 
 def _run(cmd):
@@ -41,6 +42,28 @@ def test_bench_single_rank_runs_comm_path():
     res = _run([sys.executable, "bench.py"] + ARGS)
     _check(res, 1)
     assert "forced" in res["config"]["comm"]  # N=1 runs the same all-reduce path as N>1
+
+
+def test_bench_plain_run_dumps_reproducible_outputs(tmp_path):
+    """Without --full the comm-statistics phase is skipped; --dump-outputs writes the last timed step's loss,
+    parameters and gradients as float32 .npy files that two runs with the same arguments reproduce exactly,
+    however many warmup steps the clock gave each."""
+    import numpy as np
+
+    dumps = []
+    for name in ("a", "b"):
+        res = _run([sys.executable, "bench.py"] + PLAIN + ["--dump-outputs", str(tmp_path / name)])
+        assert res["steps"] == 2 and res["ms_per_step"] > 0
+        assert set(res["comm_stats"]) == {"bucket_bytes"}
+        dumps.append({f: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))})
+    a, b = dumps
+    assert {"loss.npy", "param.fc1.weight.npy", "grad.fc1.weight.npy", "param.conv1.bias.npy"} <= set(a)
+    assert set(a) == set(b) and len(a) == 17  # loss + 8 parameters + 8 gradients
+    assert abs(float(a["loss.npy"]) - res["final_loss"]) < 1e-5
+    for f in a:
+        assert a[f].dtype == np.float32 and np.isfinite(a[f]).all(), f
+        assert np.array_equal(a[f], b[f]), f
+    assert a["param.fc1.weight.npy"].shape == (10, 2048) and np.abs(a["grad.fc1.weight.npy"]).max() > 0
 
 
 def test_bench_self_launches_n_ranks():

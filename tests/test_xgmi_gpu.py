@@ -174,7 +174,7 @@ def test_bench_contract_two_ranks_xgmi():
     backend and prints exactly one JSON line with the contract fields."""
     env = dict(os.environ, RINGDP_GPU_BACKEND="xgmi", PYTHONPATH=ROOT, RINGDP_BENCH_MIN_WARMUP_S="0")
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "6", "--warmup", "2",
-                        "--batch-per-rank", "1024", "--comm-stats-steps", "3"],
+                        "--batch-per-rank", "1024", "--full", "--comm-stats-steps", "3"],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

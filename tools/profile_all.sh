@@ -19,12 +19,12 @@ run() {  # name timeout cmd...
 for s in ${STEPS:-tests bench prof micro}; do
   case $s in
     tests) run pytest_gpu 900 python -m pytest tests -m gpu -q -p no:cacheprovider ;;
-    bench) run bench_convnet 300 python bench.py
-           run bench_convnet_b100 300 python bench.py --batch-per-rank 100 --steps 300 --warmup 20
-           run bench_resnet18 300 python bench.py --model resnet18 --steps 30 --warmup 5
-           run bench_resnet50 400 python bench.py --model resnet50 --steps 10 --warmup 3
-           run bench_vit 400 python bench.py --model vit_b_16 --steps 10 --warmup 3
-           run bench_vit_fp8 400 python bench.py --model vit_b_16 --dtype fp8 --steps 10 --warmup 3 ;;
+    bench) run bench_convnet 300 python bench.py --full
+           run bench_convnet_b100 300 python bench.py --full --batch-per-rank 100 --steps 300 --warmup 20
+           run bench_resnet18 300 python bench.py --full --model resnet18 --steps 30 --warmup 5
+           run bench_resnet50 400 python bench.py --full --model resnet50 --steps 10 --warmup 3
+           run bench_vit 400 python bench.py --full --model vit_b_16 --steps 10 --warmup 3
+           run bench_vit_fp8 400 python bench.py --full --model vit_b_16 --dtype fp8 --steps 10 --warmup 3 ;;
     prof)  run prof_convnet 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_convnet -o run --output-format csv -- python3 bench.py --steps 50 --warmup 5 --no-graph
            run prof_resnet50 400 rocprofv3 --kernel-trace --stats -d $OUT/prof_resnet50 -o run --output-format csv -- python3 bench.py --model resnet50 --steps 5 --warmup 2 --no-graph
            run prof_vit 400 rocprofv3 --kernel-trace --stats -d $OUT/prof_vit -o run --output-format csv -- python3 bench.py --model vit_b_16 --steps 5 --warmup 2 --no-graph ;;
