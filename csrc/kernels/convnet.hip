@@ -859,8 +859,6 @@ __global__ __launch_bounds__(256) void fc1_fwd_kernel(const bf16* __restrict__ a
 //                                                           consumer: pool3 -> a3 / idx3, fc1 partials
 // Each LDS buffer has one writer phase and its readers in other phases, so every buffer is single.
 // The layouts are the separate kernels' (conv1_fwd_kernel / conv2_fwd_kernel / conv3_fwd_kernel<true>).
-// PACK: weight fragments built from the fp32 masters (pack_value) by each workgroup, and the extra
-// workgroups >= conv_blocks write the packed buffer for the backward.
 constexpr int FF_XS = 8 * C1F_CS * 2;      // 16768: conv1 input, 8 shifted copies
 constexpr int FF_X2 = 172 * C2_XRS * 2;    // 16512: a1 in conv2 operand rows (+3 dump rows)
 constexpr int FF_CT = C1I_IMG + 64;        // 3392: conv1 codes (+ dump row)
@@ -894,50 +892,32 @@ constexpr int FF_ST_BYTES = 0;
   } while (0)
 #endif
 
-template <bool PACK>
-__device__ __forceinline__ bf16x8 ff_frag(const bf16* __restrict__ packed, const PackSrc& ws, int off, int lane) {
-  bf16x8 v;
-  if (PACK) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (bf16)pack_value(off + lane * 8 + j, ws);
-  } else {
-    v = reinterpret_cast<const bf16x8*>(packed + off)[lane];
-  }
-  return v;
+// RINGDP_FF_ABLATE (diagnostic builds only, tools/build_variant.py; timing only, wrong results): bit 0 empties
+// the producer role, bit 1 the consumer role.  A compile-time constant, 0 in every normal build: nothing reads
+// the environment for it and no launch argument can select it.
+#ifndef RINGDP_FF_ABLATE
+#define RINGDP_FF_ABLATE 0
+#endif
+constexpr int FF_ABLATE = RINGDP_FF_ABLATE;
+
+__device__ __forceinline__ bf16x8 ff_frag(const bf16* __restrict__ packed, int off, int lane) {
+  return reinterpret_cast<const bf16x8*>(packed + off)[lane];
 }
 
-// In-launch weight packing (PACK): workgroups >= conv_blocks write the packed fragments and count
-// themselves done in sync[0]; a conv wave waits for all of them before its first fragment read (lane 0
-// polls with an agent-scope acquire, s_sleep between polls, bounded: the pack workgroups depend on
-// nothing, so they finish).  The last conv workgroup to finish resets both words for the next launch
-// (graph-replay safe: the counters live in a persistent pool, ops.cpp next_counter).
-__device__ __forceinline__ void ff_wait_packed(unsigned* sync, int npack) {
-  if ((threadIdx.x & 63) == 0) {
-    for (int it = 0; it < (1 << 24); ++it) {
-      if (__hip_atomic_load(sync, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) >= (unsigned)npack) break;
-      __builtin_amdgcn_s_sleep(2);
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-}
-
-// pool2 + ReLU of items [lo, hi) (item = position p, 8-channel chunk) of the staged conv2 tile -> a2 /
-// idx2 in HBM and the conv3 operand rows of buffer X3b.  Phase 3 splits the items between the producer
-// and the consumer (the producer is the long pole: 1103 vs 808 us alone at B=65536).
-// items [0, p2split) are the producer's (kernel argument; RINGDP_FF_P2, default 800 of 800 since the packed
-// pool2: phase 3 is consumer-bound (profiles/r06/fwd_stamps.md), and step times of 560 / 704 / 800 were
-// 3.335 / 3.333 / 3.325 ms, two runs each, profiles/r06/fwd_pool2/p2_resweep.txt)
+// pool2 + ReLU of the staged conv2 tile (800 items: position p, 8-channel chunk) -> a2 / idx2 in HBM and the
+// conv3 operand rows of buffer X3b.  All of it is the producer's phase 3: the consumer's phase 3 holds no pool2
+// code beside conv3's 144 weight registers (phase 3 is consumer-bound, profiles/r06/fwd_stamps.md; giving the
+// consumer a share of the items measured no faster, profiles/r06/fwd_pool2/p2_resweep.txt).
 __device__ __forceinline__ void ff_pool2(const bf16* Cs, bf16* X3b, bf16* __restrict__ a2, uint8_t* __restrict__ idx2,
-                                         int b, int t, int lo, int hi) {
-  // uniform per-image bases, 32-bit per-item offsets (no 64-bit address math per item); at most 3 items
-  // per thread (hi - lo <= 800, 256 threads per role)
+                                         int b, int t) {
+  // uniform per-image bases, 32-bit per-item offsets (no 64-bit address math per item); 3 or 4 items per
+  // thread (800 items, the producer's 256 threads)
   bf16x8* da = reinterpret_cast<bf16x8*>(a2 + (int64_t)b * 6400);
   uint2* di = reinterpret_cast<uint2*>(idx2 + (int64_t)b * 6400);
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const int it = lo + t + 256 * k;
-    if (it >= hi) break;
+    const int it = t + 256 * k;
+    if (it >= 800) break;
     const int p = it >> 3, c = (it & 7) * 8;
     const int y = (p * 205) >> 11;  // p / 10 for p < 100
     bf16x8 v;
@@ -949,28 +929,12 @@ __device__ __forceinline__ void ff_pool2(const bf16* Cs, bf16* X3b, bf16* __rest
   }
 }
 
-// software-pipelined A-fragment reads in the conv2 (producer) / conv3 (consumer) k-step loops (A/B build macros)
-// RINGDP_FF_P2_ALL (default): the producer pools all 800 pool2 items and the consumer's phase 3 holds no pool2
-// code at all (fewer live registers beside conv3's 144 weight registers); 0: the split is the run-time
-// p2split argument (RINGDP_FF_P2)
-#ifndef RINGDP_FF_P2_ALL
-#define RINGDP_FF_P2_ALL 1
-#endif
-#ifndef RINGDP_FF_KPIPE
-#define RINGDP_FF_KPIPE 0
-#endif
-// issue priority between the two waves of a SIMD (scheduling A/B through RINGDP_FF_ABLATE, results unchanged):
-// by default age decides (the older producer wave wins); bit 4: the consumer at priority 1 in phase 3; bit 5:
-// the producer at priority 1 in phases 1-2
-#ifndef RINGDP_FF_PPIPE
-#define RINGDP_FF_PPIPE 0
-#endif
-template <bool U8, bool PACK>
+template <bool U8>
 __device__ __forceinline__ void ff_producer(char* smem, const void* __restrict__ xin, const bf16* __restrict__ packed,
-                            const PackSrc& ws, const float* __restrict__ b1, const float* __restrict__ b2,
+                            const float* __restrict__ b1, const float* __restrict__ b2,
                             bf16* __restrict__ a1, uint8_t* __restrict__ idx1, bf16* __restrict__ a2,
                             uint8_t* __restrict__ idx2, int B, int b0, int bstep, int nsteps, float mean,
-                            float inv_std, float in_scale, unsigned* sync, int npack, int p2split, int prio) {
+                            float inv_std, float in_scale) {
   bf16* XS = reinterpret_cast<bf16*>(smem);
   bf16* X2 = reinterpret_cast<bf16*>(smem + FF_OFF_X2);
   uint32_t* X2u = reinterpret_cast<uint32_t*>(X2);
@@ -984,8 +948,7 @@ __device__ __forceinline__ void ff_producer(char* smem, const void* __restrict__
 #pragma unroll
   for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) bw1[nt][ks] = ff_frag<PACK>(packed, ws, P1_OFF + (nt * 2 + ks) * 512, lane);
-  if (PACK) ff_wait_packed(sync, npack);  // conv1's 32 values per lane came from the masters directly
+    for (int ks = 0; ks < 2; ++ks) bw1[nt][ks] = ff_frag(packed, P1_OFF + (nt * 2 + ks) * 512, lane);
   const float c1b0 = b1[2 * r16], c1b1 = b1[2 * r16 + 1];
   const f32x4 bias0v = {c1b0, c1b0, c1b0, c1b0}, bias1v = {c1b1, c1b1, c1b1, c1b1};
   int aoff[C1F_MT], coff[C1F_MT];
@@ -1004,7 +967,7 @@ __device__ __forceinline__ void ff_producer(char* smem, const void* __restrict__
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
-    for (int ks = 0; ks < 9; ++ks) bw2[t][ks] = ff_frag<false>(packed, ws, P2F_OFF + ((2 * wn + t) * 9 + ks) * 512, lane);
+    for (int ks = 0; ks < 9; ++ks) bw2[t][ks] = ff_frag(packed, P2F_OFF + ((2 * wn + t) * 9 + ks) * 512, lane);
   f32x4 bv2[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
@@ -1033,7 +996,6 @@ __device__ __forceinline__ void ff_producer(char* smem, const void* __restrict__
     const bool live = b < B;
     const int nb = b + bstep;
     FF_ST(0);
-    if (prio & 2) __builtin_amdgcn_s_setprio(1);
     // ---------------- phase 1: conv1 -> X2 / CT
     if (live) {
       if (nb < B) c1_load<U8>(xin, nb, tid, pu, pf);
@@ -1073,36 +1035,6 @@ __device__ __forceinline__ void ff_producer(char* smem, const void* __restrict__
       if (nb < B) c1_store<U8, 8, XC_W, C1F_CS>(XS, tid, pu, pf, mean, inv_std, in_scale);
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt) acc[mt][0] = acc[mt][1] = zero_f32x4();
-#if RINGDP_FF_PPIPE
-      // software-pipelined as the consumer's conv3 k-steps (RINGDP_FF_KPIPE)
-      {
-        auto a2_of = [&](int ks, int mt) {
-          const int shift = (ks / 3) * 13 + ks % 3;
-          return *reinterpret_cast<const bf16x8*>(X2 + (base2[mt] + shift) * C2_XRS + q8);
-        };
-        bf16x8 cur[4], nxt[4];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) cur[mt] = a2_of(0, mt);
-#pragma unroll
-        for (int ks = 0; ks < 9; ++ks) {
-          if (ks + 1 < 9) {
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) nxt[mt] = a2_of(ks + 1, mt);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) {
-            acc[mt][0] = mfma16x16x32(bw2[0][ks], cur[mt], acc[mt][0]);
-            acc[mt][1] = mfma16x16x32(bw2[1][ks], cur[mt], acc[mt][1]);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          if (ks + 1 < 9) {
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) cur[mt] = nxt[mt];
-          }
-        }
-      }
-#else
 #pragma unroll
       for (int ks = 0; ks < 9; ++ks) {
         const int shift = (ks / 3) * 13 + ks % 3;
@@ -1113,7 +1045,6 @@ __device__ __forceinline__ void ff_producer(char* smem, const void* __restrict__
           acc[mt][1] = mfma16x16x32(bw2[1][ks], a, acc[mt][1]);
         }
       }
-#endif
       // a1 / idx1 to HBM while the MFMAs drain
       uint4* og = reinterpret_cast<uint4*>(a1 + (int64_t)b * C1A_IMG);
       for (int c = tid; c < C1A_IMG / 8; c += 256)
@@ -1137,13 +1068,8 @@ __device__ __forceinline__ void ff_producer(char* smem, const void* __restrict__
     FF_ST(3);
     __syncthreads();  // [S2] Cs complete
     FF_ST(4);
-    if (prio & 2) __builtin_amdgcn_s_setprio(0);
-    // ---------------- phase 3: pool2 -> a2 / idx2 (HBM) + X3 (items [0, FF_P2_PROD); the consumer pools the rest)
-#if RINGDP_FF_P2_ALL
-    if (live) ff_pool2(Cs, X3 + (s & 1) * FF_X3H, a2, idx2, b, tid, 0, 800);
-#else
-    if (live) ff_pool2(Cs, X3 + (s & 1) * FF_X3H, a2, idx2, b, tid, 0, p2split);
-#endif
+    // ---------------- phase 3: pool2 -> a2 / idx2 (HBM) + X3
+    if (live) ff_pool2(Cs, X3 + (s & 1) * FF_X3H, a2, idx2, b, tid);
     FF_ST(5);
     __syncthreads();  // [S3] X3 complete; Cs, X2, CT free
     FF_ST(6);
@@ -1151,25 +1077,17 @@ __device__ __forceinline__ void ff_producer(char* smem, const void* __restrict__
 }
 
 // the consumer's conv3 k-steps per phase: [0, KA) beside conv1, [KA, KB) beside conv2, [KB, 18) beside pool2
-#ifndef RINGDP_FF_KA
-#define RINGDP_FF_KA 4
-#endif
-#ifndef RINGDP_FF_KB
-#define RINGDP_FF_KB 11
-#endif
-template <bool PACK>
-__device__ __forceinline__ void ff_consumer(char* smem, const bf16* __restrict__ packed, const PackSrc& ws,
+// (other splits measured the same within noise, profiles/r06/rejected/README.md)
+constexpr int FF_KA = 4, FF_KB = 11;
+__device__ __forceinline__ void ff_consumer(char* smem, const bf16* __restrict__ packed,
                             const float* __restrict__ b3, const float* __restrict__ bfc, bf16* __restrict__ a3,
-                            uint8_t* __restrict__ idx3, float* __restrict__ logits, bf16* __restrict__ a2,
-                            uint8_t* __restrict__ idx2, int Bp, int B, int b0, int bstep, int nsteps,
-                            unsigned* sync, int npack, int p2split, int prio) {
+                            uint8_t* __restrict__ idx3, float* __restrict__ logits, int B, int b0, int bstep,
+                            int nsteps) {
   bf16* X3 = reinterpret_cast<bf16*>(smem + FF_OFF_X3);
-  const bf16* Cs = reinterpret_cast<const bf16*>(smem + FF_OFF_CS);
   bf16* fw = reinterpret_cast<bf16*>(smem + FF_OFF_FW);
   float* fred = reinterpret_cast<float*>(smem + FF_OFF_FR);
   const int tid = threadIdx.x - 256, lane = tid & 63, wave = tid >> 6;
   const int r16 = lane & 15, q8 = (lane >> 4) * 8;
-  if (PACK) ff_wait_packed(sync, npack);
   // fc1 in this launch unless logits == nullptr (large batches: fc1_fwd_kernel, an MFMA pass over a3, takes
   // its ~200 VALU per lane and image out of phase 1, where the producer's conv1 epilogue is VALU-bound too)
   const bool fc = logits != nullptr;
@@ -1181,7 +1099,7 @@ __device__ __forceinline__ void ff_consumer(char* smem, const bf16* __restrict__
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
-    for (int ks = 0; ks < 18; ++ks) bw[t][ks] = ff_frag<false>(packed, ws, P3F_OFF + ((2 * wave + t) * 18 + ks) * 512, lane);
+    for (int ks = 0; ks < 18; ++ks) bw[t][ks] = ff_frag(packed, P3F_OFF + ((2 * wave + t) * 18 + ks) * 512, lane);
   float bv[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t) bv[t] = b3[32 * wave + 16 * t + r16];
@@ -1207,39 +1125,6 @@ __device__ __forceinline__ void ff_consumer(char* smem, const bf16* __restrict__
   };
   f32x4 acc[4][2];
   // conv3 k-steps [k0, k1) of the image in buffer xb
-#if RINGDP_FF_KPIPE
-  // software-pipelined: the next k-step's 4 A fragments are read before this k-step's 8 MFMAs (sched_barrier
-  // pins the order), so each LDS read has 8 MFMAs (128 cycles) to land instead of being waited on at once
-  auto a_of = [&](const bf16* xb, int ks, int mt) {
-    const int tap = ks >> 1, c0 = (ks & 1) * 32;
-    const int shift = (tap / 3) * 10 + tap % 3;
-    return *reinterpret_cast<const bf16x8*>(xb + (base[mt] + shift) * C3F_XRS + c0 + q8);
-  };
-  auto mfma_ks = [&](const bf16* xb, auto k0c, auto k1c) {
-    constexpr int k0 = decltype(k0c)::value, k1 = decltype(k1c)::value;
-    bf16x8 cur[4], nxt[4];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) cur[mt] = a_of(xb, k0, mt);
-#pragma unroll
-    for (int ks = k0; ks < k1; ++ks) {
-      if (ks + 1 < k1) {
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) nxt[mt] = a_of(xb, ks + 1, mt);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        acc[mt][0] = mfma16x16x32(cur[mt], bw[0][ks], acc[mt][0]);
-        acc[mt][1] = mfma16x16x32(cur[mt], bw[1][ks], acc[mt][1]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      if (ks + 1 < k1) {
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) cur[mt] = nxt[mt];
-      }
-    }
-  };
-#else
   auto mfma_ks = [&](const bf16* xb, auto k0c, auto k1c) {
 #pragma unroll
     for (int ks = decltype(k0c)::value; ks < decltype(k1c)::value; ++ks) {
@@ -1253,7 +1138,6 @@ __device__ __forceinline__ void ff_consumer(char* smem, const bf16* __restrict__
       }
     }
   };
-#endif
   // Step s: pool3 / fc1-partials epilogue of image s-2 and the first 4 k-steps of image s-1 (phase 1,
   // beside the producer's MFMA-light conv1), fc1 reduction of s-2 + k-steps 4-10 (phase 2), k-steps
   // 11-17 (phase 3, beside the producer's VALU-only pool2): the MFMA pipe has work in every phase.
@@ -1295,68 +1179,46 @@ __device__ __forceinline__ void ff_consumer(char* smem, const bf16* __restrict__
     if (live_m) {
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt) acc[mt][0] = acc[mt][1] = zero_f32x4();
-      mfma_ks(xb, std::integral_constant<int, 0>{}, std::integral_constant<int, RINGDP_FF_KA>{});
+      mfma_ks(xb, std::integral_constant<int, 0>{}, std::integral_constant<int, FF_KA>{});
     }
     FF_ST(1);
     __syncthreads();  // [S1]
     FF_ST(2);
     // ---------------- phase 2
     if (live_e && fc) fc_reduce(be);
-    if (live_m) mfma_ks(xb, std::integral_constant<int, RINGDP_FF_KA>{}, std::integral_constant<int, RINGDP_FF_KB>{});
+    if (live_m) mfma_ks(xb, std::integral_constant<int, FF_KA>{}, std::integral_constant<int, FF_KB>{});
     FF_ST(3);
     __syncthreads();  // [S2]
     FF_ST(4);
-    // ---------------- phase 3: the rest of the producer's pool2 (image s), k-steps 11-17
-    // phase 3 is the consumer's (fwd_stamps.md): win the SIMD's issue arbitration against the older producer wave
-    if (prio & 1) __builtin_amdgcn_s_setprio(1);
-#if !RINGDP_FF_P2_ALL
-    {
-      const int bpr = b0 + s * bstep;
-      if (bpr < Bp) ff_pool2(Cs, X3 + (s & 1) * FF_X3H, a2, idx2, bpr, tid, p2split, 800);
-    }
-#endif
-    if (live_m) mfma_ks(xb, std::integral_constant<int, RINGDP_FF_KB>{}, std::integral_constant<int, 18>{});
+    // ---------------- phase 3: k-steps 11-17
+    if (live_m) mfma_ks(xb, std::integral_constant<int, FF_KB>{}, std::integral_constant<int, 18>{});
     FF_ST(5);
     __syncthreads();  // [S3]
     FF_ST(6);
-    if (prio & 1) __builtin_amdgcn_s_setprio(0);
   }
 }
 
-template <bool U8, bool PACK>
+template <bool U8>
 __global__ __launch_bounds__(512, 1) void fused_fwd_kernel(const void* __restrict__ xin,
-                                                          const bf16* __restrict__ packed, PackSrc ws,
-                                                          bf16* __restrict__ pack_out, int conv_blocks,
+                                                          const bf16* __restrict__ packed,
                                                           const float* __restrict__ b1, const float* __restrict__ b2,
                                                           const float* __restrict__ b3, const float* __restrict__ bfc,
                                                           bf16* __restrict__ a1, uint8_t* __restrict__ idx1,
                                                           bf16* __restrict__ a2, uint8_t* __restrict__ idx2,
                                                           bf16* __restrict__ a3, uint8_t* __restrict__ idx3,
                                                           float* __restrict__ logits, int B, float mean,
-                                                          float inv_std, float in_scale, int ablate,
-                                                          unsigned* sync, int p2split) {
-  const int npack = (int)gridDim.x - conv_blocks;
-  if (PACK && (int)blockIdx.x >= conv_blocks) {
-    if (threadIdx.x < 256) pack_range(ws, pack_out, 0, blockIdx.x - conv_blocks, npack);
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(sync, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    return;
-  }
+                                                          float inv_std, float in_scale) {
   __shared__ __attribute__((aligned(16))) char ff_smem[FF_LDS + FF_ST_BYTES];
-  const int b0 = blockIdx.x, bstep = conv_blocks;
+  const int b0 = blockIdx.x, bstep = gridDim.x;
   const int nimg = b0 < B ? (B - b0 + bstep - 1) / bstep : 0;
   const int nsteps = nimg + 2;  // the consumer's MFMAs trail by one step, its epilogue by two
   // wave-uniform role split (an SGPR condition: the two roles are separate code paths, not one
   // exec-masked sequence whose live ranges the register allocator would have to overlap)
   if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) < 4)
-    ff_producer<U8, PACK>(ff_smem, xin, PACK ? pack_out : packed, ws, b1, b2, a1, idx1, a2, idx2,
-                          (ablate & 1) ? 0 : B, b0, bstep, nsteps, mean, inv_std, in_scale, sync, npack, p2split,
-                          __builtin_amdgcn_readfirstlane(ablate >> 4));
+    ff_producer<U8>(ff_smem, xin, packed, b1, b2, a1, idx1, a2, idx2, (FF_ABLATE & 1) ? 0 : B, b0, bstep, nsteps,
+                    mean, inv_std, in_scale);
   else
-    ff_consumer<PACK>(ff_smem, PACK ? pack_out : packed, ws, b3, bfc, a3, idx3, logits, a2, idx2,
-                      (ablate & 1) ? 0 : B, (ablate & 2) ? 0 : B, b0, bstep, nsteps, sync, npack, p2split,
-                      __builtin_amdgcn_readfirstlane(ablate >> 4));
+    ff_consumer(ff_smem, packed, b3, bfc, a3, idx3, logits, (FF_ABLATE & 2) ? 0 : B, b0, bstep, nsteps);
 #ifdef RINGDP_FF_STAMPS
   __syncthreads();
   if (blockIdx.x == FF_ST_BLK && threadIdx.x == 0 && nsteps > FF_ST_S0 + 8) {
@@ -1371,16 +1233,6 @@ __global__ __launch_bounds__(512, 1) void fused_fwd_kernel(const void* __restric
       }
   }
 #endif
-  if (PACK) {  // the last conv workgroup out re-arms the counters
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const unsigned t = __hip_atomic_fetch_add(sync + 1, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-      if (t == (unsigned)conv_blocks - 1) {
-        __hip_atomic_store(sync, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(sync + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-  }
 }
 
 // ================================================================== F3 backward
@@ -1400,7 +1252,7 @@ constexpr int FC_SLAB = 10 * 2048 + 10 + 128 + 2;  // dWfc + dbfc + db3 (the con
 // (same expression as ce_bwd_kernel, elementwise.hip) - 80 threads per group of 8 images into LDS -
 // instead of read from a [B,10] tensor: the separate ce_bwd launch disappears.
 // The body runs as its own launch (fc_bwd_kernel) or as the first workgroups of the conv3 backward launch at
-// small batches (conv3_bwd_kernel<true>, blk = that workgroup's fc index; da3m == nullptr: the conv3
+// small batches (conv3_bwd_kernel, blk = that workgroup's fc index; da3m == nullptr: the conv3
 // roles form their own compact gradient, C3Pre::load).
 template <bool kCE>
 __device__ __forceinline__ void fc_bwd_body(const bf16* __restrict__ a3, const bf16* __restrict__ packed,
@@ -1536,11 +1388,10 @@ constexpr int C3_WSLAB = 576 * 128;  // dW3t
 
 // The compact F3-backward input of one image, held in registers while the previous image is
 // computed on: d(a3) chunk + its pool3 argmax bytes (threads < 256).
-// Where the conv3 backward roles get an image's compact d(a3): the fc1 backward launch's da3m, or (small
-// batches, fc1 backward inside this launch) computed in place from a3, the logits gradient and the packed
-// fc1 weights - the same expression and order as fc_bwd_body, so the values are bit-identical.
+// What the 4-wave conv3 backward roles (small batches, fc1 backward inside their launch) form an image's
+// compact d(a3) from: a3, the logits gradient and the packed fc1 weights - the same expression and order as
+// fc_bwd_body, so the values are bit-identical to the da3m that fc_bwd_kernel leaves for the 8-wave kernel.
 struct C3Src {
-  const bf16* da3m;  // null: compute
   const bf16* a3;
   const bf16* packed;
   const float* dl;   // logits gradient, or null with ce
@@ -1550,14 +1401,9 @@ struct C3Src {
 struct C3Pre {
   bf16x8 da;
   uint2 id;
-  template <bool kFC>
   __device__ __forceinline__ void load(const C3Src& src, const uint8_t* __restrict__ idx3, int b, int tid) {
     if (tid < 256) {
       id = reinterpret_cast<const uint2*>(idx3 + (int64_t)b * 2048)[tid];
-      if (!kFC) {
-        da = reinterpret_cast<const bf16x8*>(src.da3m + (int64_t)b * 2048)[tid];
-        return;
-      }
       const int wd = tid >> 4, co0 = (tid & 15) * 8;
       const bf16x8 av = reinterpret_cast<const bf16x8*>(src.a3 + (int64_t)b * 2048)[tid];
       float g[10];
@@ -1653,7 +1499,6 @@ __device__ __forceinline__ void codes_glds(const uint8_t* __restrict__ idx2, int
 // The kx taps of an m-tile hit the same da2 words from different lanes, so a compiler barrier keeps
 // each read behind the previous write (LDS executes one wave's instructions in order).  Fixed order:
 // deterministic.
-template <bool kFC>
 __device__ __forceinline__ void conv3_dgrad_role(char* smem, const C3Src& src, const uint8_t* __restrict__ idx3,
                                  const uint8_t* __restrict__ idx2, const bf16* __restrict__ packed,
                                  bf16* __restrict__ dz2, int b_first, int b_end, int b_step) {
@@ -1723,7 +1568,7 @@ __device__ __forceinline__ void conv3_dgrad_role(char* smem, const C3Src& src, c
   };
   C3Pre pre;
   int b = b_first;
-  if (b < b_end) pre.template load<kFC>(src, idx3, b, tid);
+  if (b < b_end) pre.load(src, idx3, b, tid);
   for (; b < b_end; b += b_step) {
     __syncthreads();  // previous image fully consumed (P, DA, AM)
     c3_expand(pre, tid, [&](int r) {
@@ -1732,7 +1577,7 @@ __device__ __forceinline__ void conv3_dgrad_role(char* smem, const C3Src& src, c
     });
     codes_glds(idx2, b, AM, wave, lane);  // this image's codes land during the MFMA phase
     const int nb = b + b_step;
-    if (nb < b_end) pre.template load<kFC>(src, idx3, nb, tid);
+    if (nb < b_end) pre.load(src, idx3, nb, tid);
     __syncthreads();
     mfma_phase();
     c_dma_wait();
@@ -1772,7 +1617,6 @@ __device__ __forceinline__ void conv3_dgrad_role(char* smem, const C3Src& src, c
 
 // wgrad: workgroup half h of an image slice covers n-tiles 18h..18h+17 of dW3t [576][128];
 // wave (wm, wn) owns m-tiles (co) 4wm..4wm+3 x n-tiles 18h + 9wn .. +8.
-template <bool kFC>
 __device__ __forceinline__ void conv3_wgrad_role(char* smem, const bf16* __restrict__ a2, const C3Src& src,
                                  const uint8_t* __restrict__ idx3, float* __restrict__ slabs, int B,
                                  int nslices, int slice, int h) {
@@ -1792,7 +1636,7 @@ __device__ __forceinline__ void conv3_wgrad_role(char* smem, const bf16* __restr
   const int b_lo = slice * per, b_hi = min(B, b_lo + per);
   C3Pre pre;
   if (b_lo < b_hi) {
-    pre.template load<kFC>(src, idx3, b_lo, tid);
+    pre.load(src, idx3, b_lo, tid);
     a2_glds(a2, b_lo, R, wave, lane, 4);
   }
   for (int b = b_lo; b < b_hi; ++b) {
@@ -1802,7 +1646,7 @@ __device__ __forceinline__ void conv3_wgrad_role(char* smem, const bf16* __restr
     a2_relayout(R, X, tid, 256);
     __syncthreads();  // D, X complete; R free
     if (b + 1 < b_hi) {  // lands during the MFMAs
-      pre.template load<kFC>(src, idx3, b + 1, tid);
+      pre.load(src, idx3, b + 1, tid);
       a2_glds(a2, b + 1, R, wave, lane, 4);
     }
 #pragma unroll
@@ -1842,34 +1686,31 @@ __device__ __forceinline__ void conv3_wgrad_role(char* smem, const bf16* __restr
   }
 }
 
-// kFC (small batches): workgroups [0, n_fc) run the fc1 backward (weight / bias gradient slabs only) and the
-// conv3 roles form each image's compact gradient themselves (C3Src without da3m): the fc1 backward launch
-// disappears.  One workgroup per CU then (the compact-gradient load holds the fc1 weights in registers).
-template <bool kFC>
-__global__ __launch_bounds__(256, kFC ? 1 : 2) void conv3_bwd_kernel(const bf16* __restrict__ a2,
-                                                                     const uint8_t* __restrict__ idx2, C3Src src,
-                                                                     const uint8_t* __restrict__ idx3,
-                                                                     const bf16* __restrict__ packed,
-                                                                     bf16* __restrict__ dz2, int B,
-                                                                     float* __restrict__ slabs, int n_wgrad,
-                                                                     int n_dgrad, int b_dgrad, int n_fc,
-                                                                     float* __restrict__ fc_slabs, int fc_n_imgs) {
+// The small-batch launch (B <= fc_in_c3_max_batch; larger batches: conv3_bwd8_kernel below): workgroups
+// [0, n_fc) run the fc1 backward (weight / bias gradient slabs only) and the conv3 roles form each image's
+// compact gradient themselves (C3Pre::load): no fc1 backward launch.  The register budget is one workgroup's
+// per SIMD (the compact-gradient load holds the fc1 weights in registers).
+__global__ __launch_bounds__(256, 1) void conv3_bwd_kernel(const bf16* __restrict__ a2,
+                                                           const uint8_t* __restrict__ idx2, C3Src src,
+                                                           const uint8_t* __restrict__ idx3,
+                                                           const bf16* __restrict__ packed, bf16* __restrict__ dz2,
+                                                           int B, float* __restrict__ slabs, int n_wgrad,
+                                                           int n_dgrad, int b_dgrad, int n_fc,
+                                                           float* __restrict__ fc_slabs, int fc_n_imgs) {
   __shared__ __attribute__((aligned(16))) char smem[C3B_LDS];
   int blk = blockIdx.x;
-  if (kFC) {
-    if (blk < n_fc) {
-      if (src.dl)
-        fc_bwd_body<false>(src.a3, packed, src.dl, nullptr, fc_slabs, B, fc_n_imgs, src.ce, blk);
-      else
-        fc_bwd_body<true>(src.a3, packed, nullptr, nullptr, fc_slabs, B, fc_n_imgs, src.ce, blk);
-      return;
-    }
-    blk -= n_fc;
+  if (blk < n_fc) {
+    if (src.dl)
+      fc_bwd_body<false>(src.a3, packed, src.dl, nullptr, fc_slabs, B, fc_n_imgs, src.ce, blk);
+    else
+      fc_bwd_body<true>(src.a3, packed, nullptr, nullptr, fc_slabs, B, fc_n_imgs, src.ce, blk);
+    return;
   }
+  blk -= n_fc;
   int b_first = blk, b_end = b_dgrad, b_step = n_dgrad;
   if (blk >= n_dgrad) {
     const int w = blk - n_dgrad;
-    conv3_wgrad_role<kFC>(smem, a2, src, idx3, slabs, B, n_wgrad, w >> 1, w & 1);
+    conv3_wgrad_role(smem, a2, src, idx3, slabs, B, n_wgrad, w >> 1, w & 1);
     // images [b_dgrad, B) of the data gradient go to the wgrad workgroups once their slice is done: a
     // dgrad workgroup is slower per image than its wgrad neighbour (pool2 backward, barrier phases), so
     // with one of each per CU the wgrad half would otherwise idle (static split: deterministic)
@@ -1879,7 +1720,7 @@ __global__ __launch_bounds__(256, kFC ? 1 : 2) void conv3_bwd_kernel(const bf16*
     b_end = B;
     b_step = 2 * n_wgrad;
   }
-  conv3_dgrad_role<kFC>(smem, src, idx3, idx2, packed, dz2, b_first, b_end, b_step);  // one call site: inlined
+  conv3_dgrad_role(smem, src, idx3, idx2, packed, dz2, b_first, b_end, b_step);  // one call site: inlined
 }
 
 // ---- conv3 backward with 8-wave workgroups (batches above fc_in_c3_max_batch: the fc1 backward launch
@@ -2007,10 +1848,19 @@ __device__ __forceinline__ void c3_pool2_bwd(const float* DA, const uint8_t* AM,
   }
 }
 
+// RINGDP_C3_ABLATE (diagnostic builds only, tools/build_variant.py; timing only, wrong results): bit 0 skips the
+// pool2 backward of the 8-wave conv3 backward, bit 1 its dgrad MFMA phase, bit 2 its weight gradient.  A
+// compile-time constant, 0 in every normal build: nothing reads the environment for it and no launch argument
+// can select it.
+#ifndef RINGDP_C3_ABLATE
+#define RINGDP_C3_ABLATE 0
+#endif
+constexpr int C3_ABLATE = RINGDP_C3_ABLATE;
+
 __device__ __forceinline__ void conv3_dgrad8_role(char* smem, const bf16* __restrict__ da3m,
                                                   const uint8_t* __restrict__ idx3, const uint8_t* __restrict__ idx2,
                                                   const bf16* __restrict__ packed, bf16* __restrict__ dz2, int b_first,
-                                                  int b_end, int b_step, int ablate) {
+                                                  int b_end, int b_step) {
   auto Pb = [&](int k) { return reinterpret_cast<bf16*>(smem + k * C3D_P); };
   auto DAb = [&](int k) { return reinterpret_cast<float*>(smem + 2 * C3D_P + k * C3V_DA); };
   // pool2 codes of image j in AM[j & 1], issued in step j (pool2 of image j runs in step j+1)
@@ -2028,9 +1878,6 @@ __device__ __forceinline__ void conv3_dgrad8_role(char* smem, const bf16* __rest
   const int n = b_first < b_end ? (b_end - b_first + b_step - 1) / b_step : 0;
   // the zero rows of both dz3 images stay zero; the interiors are rewritten per image
   for (int c = tid; c < 2 * C3D_P / 16; c += 512) reinterpret_cast<bf16x8*>(smem)[c] = zero_bf16x8();
-  // RINGDP_C3_ABLATE / RINGDP_C12_ABLATE bit 3 (a scheduling A/B, results unchanged): the younger (VALU / DMA)
-  // half at issue priority 1 (MI355X_MICROARCH: two waves per SIMD, static priority)
-  if ((ablate & 8) && wave >= 4) __builtin_amdgcn_s_setprio(1);
   if (wave < 4) {
     // ---- MFMA waves: wave w owns input channels 16w..16w+15 (as conv3_dgrad_role)
     const int r16 = lane & 15, q8 = (lane >> 4) * 8, c4 = (lane >> 4) * 4;
@@ -2046,7 +1893,7 @@ __device__ __forceinline__ void conv3_dgrad8_role(char* smem, const bf16* __rest
     lds_barrier();  // [B0] zero rows
     lds_barrier();  // [B1] image 0 expanded
     for (int s = 0; s <= n; ++s) {
-      if (s < n && !(ablate & 2)) {
+      if (s < n && !(C3_ABLATE & 2)) {
         const bf16* P = Pb(s & 1);
         float* DA = DAb(s & 1);
         // the 13 (m-tile, ky) groups with a non-zero dz3 row, in order; group g+1's 4 B fragments are read
@@ -2135,7 +1982,7 @@ __device__ __forceinline__ void conv3_dgrad8_role(char* smem, const bf16* __rest
         c3s_pre(Sb((s + 1) & 1), vt, pre);
         c3_expand(pre, vt, row_ptr(Pb((s + 1) & 1)));
       }
-      if (s >= 1 && vt < 176 && !(ablate & 1)) c3_pool2_bwd(DAb((s - 1) & 1), AMb((s - 1) & 1), dz2, b_first + (s - 1) * b_step, vt);
+      if (s >= 1 && vt < 176 && !(C3_ABLATE & 1)) c3_pool2_bwd(DAb((s - 1) & 1), AMb((s - 1) & 1), dz2, b_first + (s - 1) * b_step, vt);
       // (issuing image s+1's codes a step earlier and leaving them in flight measured slower)
       if (dma) c_dma_wait();
       lds_barrier();
@@ -2258,18 +2105,18 @@ __global__ __launch_bounds__(512, 1) void conv3_bwd8_kernel(const bf16* __restri
                                                            const bf16* __restrict__ da3m, const uint8_t* __restrict__ idx3,
                                                            const bf16* __restrict__ packed, bf16* __restrict__ dz2,
                                                            int B, float* __restrict__ slabs, int n_wgrad, int n_dgrad,
-                                                           int b_dgrad, int ablate) {
+                                                           int b_dgrad) {
   __shared__ __attribute__((aligned(16))) char smem[C3V_LDS];
   const int blk = blockIdx.x;
   if (blk < n_dgrad) {
-    conv3_dgrad8_role(smem, da3m, idx3, idx2, packed, dz2, blk, b_dgrad, n_dgrad, ablate);
+    conv3_dgrad8_role(smem, da3m, idx3, idx2, packed, dz2, blk, b_dgrad, n_dgrad);
     return;
   }
   const int w = blk - n_dgrad;
-  if (!(ablate & 4)) conv3_wgrad8_role(smem, a2, da3m, idx3, slabs, B, n_wgrad, w);
+  if (!(C3_ABLATE & 4)) conv3_wgrad8_role(smem, a2, da3m, idx3, slabs, B, n_wgrad, w);
   if (dz2 == nullptr || b_dgrad >= B) return;
   __syncthreads();  // LDS changes role
-  conv3_dgrad8_role(smem, da3m, idx3, idx2, packed, dz2, b_dgrad + w, B, n_wgrad, ablate);
+  conv3_dgrad8_role(smem, da3m, idx3, idx2, packed, dz2, b_dgrad + w, B, n_wgrad);
 }
 
 __device__ __forceinline__ bf16x8 ones_column_frag(int lane) {
@@ -2814,6 +2661,18 @@ constexpr int C12V_WG = 3 * (C2W_D + C2W_X);                           // 108144
 constexpr int C12V_LDS = C12V_DG > C12V_WG ? C12V_DG : C12V_WG;
 static_assert(C12V_LDS <= 160 * 1024 && C1I_IMG % 16 == 0, "conv12 backward (8-wave) LDS");
 
+// RINGDP_C12_ABLATE (diagnostic builds only, tools/build_variant.py; timing only, wrong results): bit 0 skips
+// conv1's weight gradient in the 8-wave conv12 backward, bit 1 the conv2 dgrad MFMAs, bit 2 the conv2 weight
+// gradient.  A compile-time constant, 0 in every normal build: nothing reads the environment for it.
+// Unlike the other two ablation macros it still reaches its kernel as the run-time argument `ablate` (the
+// launcher passes this constant, nothing else), with the parent's uses of that argument unchanged, bit 3 (the
+// VALU / DMA half at issue priority 1) included: with the argument folded away conv12_bwd8_kernel measured
+// 2.3 % slower (917.6 vs 896.8 us, profiles/r07/variant_removal/README.md), and that schedule is not chased here.
+#ifndef RINGDP_C12_ABLATE
+#define RINGDP_C12_ABLATE 0
+#endif
+constexpr int C12_ABLATE = RINGDP_C12_ABLATE;
+
 template <bool U8>
 __device__ __forceinline__ void conv12_dgrad8_role(char* smem, const void* __restrict__ xin,
                                                    const uint8_t* __restrict__ idx1, const bf16* __restrict__ dz2,
@@ -2831,8 +2690,6 @@ __device__ __forceinline__ void conv12_dgrad8_role(char* smem, const void* __res
   for (int c = tid; c < (2 * (C2D_P + C12_O) + 3 * C12_XS) / 16; c += 512)
     reinterpret_cast<bf16x8*>(smem)[c] = zero_bf16x8();
   __syncthreads();
-  // RINGDP_C3_ABLATE / RINGDP_C12_ABLATE bit 3 (a scheduling A/B, results unchanged): the younger (VALU / DMA)
-  // half at issue priority 1 (MI355X_MICROARCH: two waves per SIMD, static priority)
   if ((ablate & 8) && wave >= 4) __builtin_amdgcn_s_setprio(1);
   if (wave < 4) {
     // ---- MFMA waves: m-tiles wave, wave + 4, wave + 8 (< 11), both n-tiles.  Weights are the A operand
@@ -3352,45 +3209,21 @@ void cn_sgd_flat_pack(float* p, const float* g, float* m, int64_t n, const SgdAr
 void cn_forward_fused(const void* x, bool u8, const float* const* w, const float* b1, const float* b2,
                       const float* b3, const float* bfc, void* packed, void* a1, uint8_t* idx1, void* a2,
                       uint8_t* idx2, void* a3, uint8_t* idx3, float* logits, int B, float mean, float inv_std,
-                      float in_scale, unsigned* sync, hipStream_t s, bool do_pack) {
-  const int conv = clampi(B, 1, wpc("FF", 1) * num_cus());  // 121 KiB LDS: one 512-thread workgroup per CU
-  const PackSrc ws{w[0], w[1], w[2], w[3]};
+                      float in_scale, hipStream_t s, bool do_pack) {
+  const int grid = clampi(B, 1, wpc("FF", 1) * num_cus());  // 121 KiB LDS: one 512-thread workgroup per CU
   bf16* pk = static_cast<bf16*>(packed);
   bf16 *a1b = static_cast<bf16*>(a1), *a2b = static_cast<bf16*>(a2), *a3b = static_cast<bf16*>(a3);
-  static const int ablate = [] { const char* v = getenv("RINGDP_FF_ABLATE"); return v ? atoi(v) : 0; }();
-  static const int p2split = [] { const char* v = getenv("RINGDP_FF_P2"); const int n = v ? atoi(v) : 800;
-                                  return n >= 0 && n <= 800 ? n : 800; }();
-  // In-launch packing (RINGDP_FF_INPACK=1) is correct but slow on MI355X: the pack workgroups' agent-scope
-  // release has to write their XCD's L2 back before the other XCDs may read the fragments (measured
-  // B=100: 114 us against 23 us with the separate pack launch), so it is off by default.
-  static const bool inpack = [] { const char* v = getenv("RINGDP_FF_INPACK"); return v && atoi(v) != 0; }();
-  // Pack workgroups in this launch, the conv workgroups waiting for them, only while whole CUs stay
-  // free for the pack workgroups: a conv workgroup takes a CU's entire register file (2 x 256 VGPRs per
-  // SIMD), so with a conv workgroup on every CU the pack workgroups could never start.
-  if (inpack && sync && conv <= num_cus() - 32) {
-    const int grid = conv + cdiv(PACK_TOTAL, 1024);
-    if (u8)
-      fused_fwd_kernel<true, true><<<grid, 512, 0, s>>>(x, nullptr, ws, pk, conv, b1, b2, b3, bfc, a1b, idx1, a2b,
-                                                        idx2, a3b, idx3, logits, B, mean, inv_std, in_scale, ablate,
-                                                        sync, p2split);
-    else
-      fused_fwd_kernel<false, true><<<grid, 512, 0, s>>>(x, nullptr, ws, pk, conv, b1, b2, b3, bfc, a1b, idx1, a2b,
-                                                         idx2, a3b, idx3, logits, B, mean, inv_std, in_scale, ablate,
-                                                         sync, p2split);
-    return;
-  }
-  // (do_pack false: the optimizer wrote these fragments when it last updated the weights)
-  if (do_pack) pack_weights_kernel<<<cdiv(PACK_TOTAL, 1024), 256, 0, s>>>(ws, pk);
+  // The weight pack is a launch of its own (do_pack false: the optimizer wrote these fragments when it last
+  // updated the weights); packing inside the forward launch was measured and removed (docs/ARCHITECTURE.md).
+  if (do_pack) pack_weights_kernel<<<cdiv(PACK_TOTAL, 1024), 256, 0, s>>>(PackSrc{w[0], w[1], w[2], w[3]}, pk);
   const bool fc_in = B <= fc_fused_max_batch();  // else fc1 as its own MFMA pass over a3
   float* lg = fc_in ? logits : nullptr;
   if (u8)
-    fused_fwd_kernel<true, false><<<conv, 512, 0, s>>>(x, pk, ws, nullptr, conv, b1, b2, b3, bfc, a1b, idx1, a2b,
-                                                       idx2, a3b, idx3, lg, B, mean, inv_std, in_scale, ablate,
-                                                       nullptr, p2split);
+    fused_fwd_kernel<true><<<grid, 512, 0, s>>>(x, pk, b1, b2, b3, bfc, a1b, idx1, a2b, idx2, a3b, idx3, lg, B, mean,
+                                                inv_std, in_scale);
   else
-    fused_fwd_kernel<false, false><<<conv, 512, 0, s>>>(x, pk, ws, nullptr, conv, b1, b2, b3, bfc, a1b, idx1, a2b,
-                                                        idx2, a3b, idx3, lg, B, mean, inv_std, in_scale, ablate,
-                                                        nullptr, p2split);
+    fused_fwd_kernel<false><<<grid, 512, 0, s>>>(x, pk, b1, b2, b3, bfc, a1b, idx1, a2b, idx2, a3b, idx3, lg, B, mean,
+                                                 inv_std, in_scale);
   if (!fc_in) fc1_fwd_kernel<<<cdiv(B, 16 * FC1_G), 256, 0, s>>>(a3b, pk, bfc, logits, B);
 }
 
@@ -3433,25 +3266,9 @@ static int min_slab_images(const char* env, int dflt) {
   return n >= 1 && n <= 64 ? n : dflt;
 }
 
-// 8-wave conv3 backward (conv3_bwd8_kernel): batches above fc_in_c3_max_batch, RINGDP_C3_V3=0 keeps the
-// 4-wave kernel (A/B)
-static bool c3_v3(int B) {
-  static const bool on = [] {
-    const char* v = getenv("RINGDP_C3_V3");
-    return !(v && v[0] == '0');
-  }();
-  return on && B > fc_in_c3_max_batch();
-}
-
-// timing-only ablations of the 8-wave conv3 backward (wrong results): bit 0 skips the pool2 backward,
-// bit 1 the dgrad MFMA phase, bit 2 the weight gradient (RINGDP_C3_ABLATE)
-static int c3_ablate() {
-  static const int v = [] {
-    const char* e = getenv("RINGDP_C3_ABLATE");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
+// 8-wave conv3 backward (fc_bwd_kernel + conv3_bwd8_kernel): batches above fc_in_c3_max_batch; up to it the
+// 4-wave kernel with fc1's backward inside its launch (conv3_bwd_kernel)
+static bool c3_v3(int B) { return B > fc_in_c3_max_batch(); }
 
 // dgrad and wgrad do about the same MFMA work per image (624 / 576 MFMAs); measured best split 0.5-0.6 of
 // the workgroup slots (B=32768).
@@ -3511,25 +3328,9 @@ static void c2_split(int B, bool dgrad, int& nd, int& ws) {
 
 // fused conv2 backward + conv1 wgrad: the dgrad role also does conv1 wgrad (104 MFMAs per image on top
 // of conv2 dgrad's 396; conv2 wgrad: 304)
-// 8-wave conv2 backward + conv1 wgrad (conv12_bwd8_kernel): the conv3 bwd8 batches; RINGDP_C12_V3=0 keeps the
-// 8-wave unpipelined kernel (A/B)
-static bool c12_v3(int B) {
-  static const bool on = [] {
-    const char* v = getenv("RINGDP_C12_V3");
-    return !(v && v[0] == '0');
-  }();
-  return on && B > fc_in_c3_max_batch();
-}
-
-// timing-only ablations of the 8-wave conv12 backward (wrong results): bit 0 skips conv1 wgrad, bit 1 the
-// conv2 dgrad MFMAs, bit 2 the conv2 weight gradient (RINGDP_C12_ABLATE)
-static int c12_ablate() {
-  static const int v = [] {
-    const char* e = getenv("RINGDP_C12_ABLATE");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
+// wave-specialised conv2 backward + conv1 wgrad (conv12_bwd8_kernel): the conv3 bwd8 batches; up to
+// fc_in_c3_max_batch the unpipelined kernel (conv12_bwd_kernel)
+static bool c12_v3(int B) { return B > fc_in_c3_max_batch(); }
 
 static void c12_split(int B, int& nd, int& ws) {
   const int cus = num_cus();
@@ -3585,26 +3386,18 @@ void cn_conv3_fc_bwd(const void* a2, const uint8_t* idx2, const void* a3, const 
   const bf16* a3b = static_cast<const bf16*>(a3);
   const bf16* pk = static_cast<const bf16*>(packed);
   const CeFuse cef = ce ? *ce : CeFuse{};
-  if (B <= fc_in_c3_max_batch()) {  // fc1 backward inside the conv3 backward launch
-    const C3Src src{nullptr, a3b, pk, ce ? nullptr : dl, cef};
-    conv3_bwd_kernel<true><<<fs + nd + 2 * ws, 256, 0, s>>>(static_cast<const bf16*>(a2), idx2, src, idx3, pk,
-                                                             static_cast<bf16*>(dz2), B, c3_slabs, ws, nd,
-                                                             c3_dgrad_images(B, nd), fs, fc_slabs, fc_imgs_host(B));
+  if (!c3_v3(B)) {  // fc1 backward inside the conv3 backward launch
+    const C3Src src{a3b, pk, ce ? nullptr : dl, cef};
+    conv3_bwd_kernel<<<fs + nd + 2 * ws, 256, 0, s>>>(static_cast<const bf16*>(a2), idx2, src, idx3, pk,
+                                                       static_cast<bf16*>(dz2), B, c3_slabs, ws, nd,
+                                                       c3_dgrad_images(B, nd), fs, fc_slabs, fc_imgs_host(B));
   } else {
     if (ce)
       fc_bwd_kernel<true><<<fs, 256, 0, s>>>(a3b, pk, nullptr, static_cast<bf16*>(da3m), fc_slabs, B, fc_imgs_host(B), cef);
     else
       fc_bwd_kernel<false><<<fs, 256, 0, s>>>(a3b, pk, dl, static_cast<bf16*>(da3m), fc_slabs, B, fc_imgs_host(B), cef);
-    if (c3_v3(B)) {
-      conv3_bwd8_kernel<<<nd + ws, 512, 0, s>>>(static_cast<const bf16*>(a2), idx2, static_cast<const bf16*>(da3m), idx3,
-                                               pk, static_cast<bf16*>(dz2), B, c3_slabs, ws, nd, c3_dgrad_images(B, nd),
-                                               c3_ablate());
-    } else {
-      const C3Src src{static_cast<const bf16*>(da3m), a3b, pk, dl, cef};
-      conv3_bwd_kernel<false><<<nd + 2 * ws, 256, 0, s>>>(static_cast<const bf16*>(a2), idx2, src, idx3, pk,
-                                                         static_cast<bf16*>(dz2), B, c3_slabs, ws, nd,
-                                                         c3_dgrad_images(B, nd), 0, nullptr, 0);
-    }
+    conv3_bwd8_kernel<<<nd + ws, 512, 0, s>>>(static_cast<const bf16*>(a2), idx2, static_cast<const bf16*>(da3m), idx3,
+                                             pk, static_cast<bf16*>(dz2), B, c3_slabs, ws, nd, c3_dgrad_images(B, nd));
   }
   ReduceList r{seg(c3_slabs, C3_WSLAB, 0, 576 * 128, ws, dw3, 1, 64, 128),
                seg(fc_slabs, FC_SLAB, 20490, 128, fs, db3), seg(fc_slabs, FC_SLAB, 0, 20480, fs, dwfc, 2),
@@ -3641,10 +3434,10 @@ void cn_conv12_bwd(const void* x, bool u8, const uint8_t* idx1, const void* a1, 
   if (c12_v3(B)) {
     if (u8)
       conv12_bwd8_kernel<true><<<nd + ws, 512, 0, s>>>(x, idx1, a1b, dzb, pk, B, mean, inv_std, in_scale, slabs2, ws,
-                                                       slabs1, nd, c12_ablate());
+                                                       slabs1, nd, C12_ABLATE);
     else
       conv12_bwd8_kernel<false><<<nd + ws, 512, 0, s>>>(x, idx1, a1b, dzb, pk, B, mean, inv_std, in_scale, slabs2, ws,
-                                                        slabs1, nd, c12_ablate());
+                                                        slabs1, nd, C12_ABLATE);
   } else if (u8)
     conv12_bwd_kernel<true><<<nd + ws, 512, 0, s>>>(x, idx1, a1b, dzb, pk, B, mean, inv_std, in_scale, slabs2, ws,
                                                     slabs1, nd);

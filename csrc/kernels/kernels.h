@@ -211,11 +211,12 @@ void cn_conv3_fc_fwd(const void* a2, const void* packed, const float* b3, const 
                      void* a3, uint8_t* idx3, int B, hipStream_t s);
 
 // F1+F2+F3 in one launch (conv1 -> conv2 -> conv3 + fc1 per image, a1 / a2 kept in LDS between the
-// layers; also packs the bf16 weight fragments into `packed` for the backward).  w = {w1, w2, w3, wfc}.
+// layers), after a pack launch that writes the bf16 weight fragments of w = {w1, w2, w3, wfc} into `packed`
+// when do_pack (else `packed` already holds them).
 void cn_forward_fused(const void* x, bool u8, const float* const* w, const float* b1, const float* b2,
                       const float* b3, const float* bfc, void* packed, void* a1, uint8_t* idx1, void* a2,
                       uint8_t* idx2, void* a3, uint8_t* idx3, float* logits, int B, float mean, float inv_std,
-                      float in_scale, unsigned* sync, hipStream_t s, bool do_pack = true);
+                      float in_scale, hipStream_t s, bool do_pack = true);
 // SGD over the flat parameter range that also writes the updated ConvNet weights into their packed bf16
 // fragments (cn_pack_weights layout); offsets[4]: first flat element of conv1 / conv2 / conv3 / fc1 weight
 void cn_sgd_flat_pack(float* p, const float* g, float* m, int64_t n, const SgdArgs& a, const int64_t* offsets,

@@ -1,24 +1,30 @@
 """Autograd Functions for the MNIST ConvNet hot path (csrc/kernels/convnet.hip).
 
-Forward is three fused blocks (reference layers ref/launch_dist.py:35-41):
+The whole forward (reference layers ref/launch_dist.py:35-41) is ONE launch, ``C.cn_forward_fused``: conv1 +
+ReLU + pool1 (+ fused ToTensor/Normalize for uint8 input), conv2 + ReLU + overlapping pool2, conv3 + ReLU +
+pool3 + fc1, with a1 / a2 handed from layer to layer in LDS.  The autograd graph still has two nodes, because
+the backward is two blocks whose gradients become final at different times:
 
-* ``_Conv1``  conv1 + ReLU + pool1 (+ fused ToTensor/Normalize for uint8 input) -> a1
-* ``_Conv2``  conv2 + bias + ReLU + overlapping pool2 -> a2 and one pool2 code byte per value
-* ``_Conv3FC``  conv3 + ReLU + pool3 + view + fc1 -> logits
+* ``_Conv12``   conv1 + conv2.  Its forward launches NOTHING: it only adopts the preallocated buffers
+  (a1, idx1, a2, idx2, packed weights) that the launch below fills, so that its backward finds them saved.
+* ``_Conv3FC``  conv3 + fc1.  Its forward issues the one launch, which computes every layer and writes
+  ``_Conv12``'s buffers as well as its own (a3, idx3, logits); the launch is stream-ordered before any
+  backward kernel that reads them.
 
-By default conv1 and conv2 form one node (``_Conv12``) whose backward is a single fused kernel: conv2's
-data gradient da1 stays in LDS and feeds conv1's weight gradient directly.
+``_Conv12``'s backward is a single fused kernel (conv2's data gradient da1 stays in LDS and feeds conv1's
+weight gradient directly); a partially frozen conv1 / conv2 takes the separate conv2-backward and
+conv1-weight-gradient kernels instead.
 
-conv2's pre-activation z2 is never materialised.  ``_Conv2`` returns a zero-stride placeholder
+conv2's pre-activation z2 is never materialised.  ``_Conv12`` returns a zero-stride placeholder
 for it (autograd's handle on "the gradient of conv2's output") next to the real activations;
 ``_Conv3FC``'s backward scatters d(a2) through the pool2 codes straight into dz2, so conv2's
 backward is a plain linear-layer backward and pool2/ReLU backward costs no extra pass over
 memory.  Weights live as bf16 MFMA fragments (``C.cn_pack_weights`` layout) next to the fp32 master
-parameters; on the default path ringdp.optim.SGD writes the fragments as it updates the masters
-(``PackState``), so the forward packs only when no optimizer step wrote them since the last forward
-(``invalidate_pack`` covers raw writes in between).  Autograd fires parameter hooks block by block - fc1/conv3 grads are final after
-``_Conv3FC.backward`` - so ringdp's reducer starts the first bucket all-reduce while conv2/conv1
-backward kernels still run.
+parameters; ringdp.optim.SGD writes the fragments as it updates the masters (``PackState``), so the
+forward packs (a launch of its own before the fused one) only when no optimizer step wrote them since the
+last forward (``invalidate_pack`` covers raw writes in between).  Autograd fires parameter hooks block by
+block - fc1/conv3 grads are final after ``_Conv3FC.backward`` - so ringdp's reducer starts the first bucket
+all-reduce while conv2/conv1 backward kernels still run.
 """
 from __future__ import annotations
 
@@ -30,11 +36,6 @@ import torch
 from .._native import C
 from . import grad_buffer
 
-# RINGDP_CN_FUSE12=0: conv1 / conv2 as separate autograd nodes with their own backward kernels (A/B)
-_FUSE12 = os.environ.get("RINGDP_CN_FUSE12", "1") != "0"
-# RINGDP_CN_FUSED_FWD=0: the three-launch forward (conv1+pack / conv2 / conv3+fc1) instead of the
-# whole-forward kernel (weight pack + cn_forward_fused; B=65536: forward 1469 -> 1390 us, B=100: 28 -> 23 us)
-_FUSED_FWD = os.environ.get("RINGDP_CN_FUSED_FWD", "1") != "0"
 # RINGDP_CN_DEFER_REDUCE=1: the conv3 / fc1 weight-gradient reduction rides in conv12's reduction launch.
 # Opt-in: while deferred, the DDP slots of w3/b3/wfc/bfc hold stale values, and nothing in autograd lets
 # this node prove that no other producer (an L2 term on the weights, a tied use) makes the engine sum the
@@ -73,65 +74,16 @@ MNIST_MEAN = 0.1307
 MNIST_STD = 0.3081
 
 
-class _Conv1(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w, b, packed, mean, std, in_scale):
-        a1, idx = C.cn_conv1_fwd(x, packed, b, mean, std, in_scale)
-        ctx.save_for_backward(x, idx)
-        ctx.params = (w, b)
-        ctx.norm = (mean, std, in_scale)
-        return a1
-
-    @staticmethod
-    def backward(ctx, da1):
-        x, idx = ctx.saved_tensors
-        w, b = ctx.params
-        need_w, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        if not (need_w or need_b):
-            return (None,) * 7
-        dw, db = grad_buffer(w), grad_buffer(b)
-        C.cn_conv1_wgrad(x, da1.contiguous(), idx, dw, db, *ctx.norm)
-        return None, (dw if need_w else None), (db if need_b else None), None, None, None, None
-
-
-class _Conv2(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, a1, w, b, packed):
-        a2, idx2 = C.cn_conv2_fwd(a1, packed, b)
-        z2 = a2.new_empty((1, 1, 1, 1)).expand(a1.shape[0], 11, 11, 64)  # placeholder, never read
-        ctx.mark_non_differentiable(a2, idx2)
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(a1, packed)
-        ctx.params = (w, b)
-        return z2, a2, idx2
-
-    @staticmethod
-    def backward(ctx, dz2, _da2, _didx2):
-        a1, packed = ctx.saved_tensors
-        w, b = ctx.params
-        C.cn_flush_reduce(a1.get_device())
-        dw, db = grad_buffer(w), grad_buffer(b)
-        need_in = ctx.needs_input_grad[0]
-        da1 = C.cn_conv2_bwd(a1, dz2.contiguous(), packed, need_in, dw, db)
-        return (da1 if need_in else None, dw if ctx.needs_input_grad[1] else None,
-                db if ctx.needs_input_grad[2] else None, None)
-
-
 class _Conv12(torch.autograd.Function):
     """conv1 + pool1 and conv2 + pool2 as one autograd node: the backward is one fused kernel
-    (conv2 dgrad + wgrad, conv1 wgrad on the LDS-resident da1) and one reduction launch."""
+    (conv2 dgrad + wgrad, conv1 wgrad on the LDS-resident da1) and one reduction launch.  The forward
+    launches nothing (module docstring): ``bufs`` are still empty when it returns."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, w3, wfc, mean, std, in_scale, bufs=None):
-        if bufs is not None:
-            # fused forward: _Conv3FC's launch (cn_forward_fused) fills these buffers, stream-ordered
-            # before any backward kernel reads them
-            a1, idx1, a2, idx2, packed = bufs
-        else:
-            # conv1's launch also packs every layer's bf16 MFMA fragments (w3 / wfc arrive detached:
-            # this node only reads them for the packing)
-            a1, idx1, packed = C.cn_conv1_fwd_pack(x, w1, w2, w3, wfc, b1, mean, std, in_scale)
-            a2, idx2 = C.cn_conv2_fwd(a1, packed, b2)
+    def forward(ctx, x, w1, b1, w2, b2, mean, std, in_scale, bufs):
+        # _Conv3FC's launch (cn_forward_fused) fills these buffers, stream-ordered before any backward
+        # kernel reads them
+        a1, idx1, a2, idx2, packed = bufs
         z2 = a2.new_empty((1, 1, 1, 1)).expand(a1.shape[0], 11, 11, 64)  # placeholder, never read
         ctx.mark_non_differentiable(a2, idx2, packed)
         ctx.set_materialize_grads(False)
@@ -150,7 +102,7 @@ class _Conv12(torch.autograd.Function):
             dw1, db1, dw2, db2 = (grad_buffer(t) for t in (w1, b1, w2, b2))
             # also launches a reduction _Conv3FC / _HeadCE deferred into this one
             C.cn_conv12_bwd(x, idx1, a1, dz2, packed, dw2, db2, dw1, db1, *ctx.norm)
-            return None, dw1, db1, dw2, db2, None, None, None, None, None, None
+            return None, dw1, db1, dw2, db2, None, None, None, None
         # partially frozen: the separate kernels
         C.cn_flush_reduce(x.get_device())
         need_c1 = n[1] or n[2]
@@ -161,18 +113,19 @@ class _Conv12(torch.autograd.Function):
             dw1, db1 = grad_buffer(w1), grad_buffer(b1)
             C.cn_conv1_wgrad(x, da1, idx1, dw1, db1, *ctx.norm)
         return (None, dw1 if n[1] else None, db1 if n[2] else None, dw2 if n[3] else None,
-                db2 if n[4] else None, None, None, None, None, None, None)
+                db2 if n[4] else None, None, None, None, None)
 
 
 class _Conv3FC(torch.autograd.Function):
+    """conv3 + pool3 + fc1 as an autograd node; its forward is the launch of the WHOLE network's forward
+    (module docstring): ``fused`` = (x, w1, b1, w2, b2, mean, std, in_scale, a1, idx1, do_pack) carries what
+    the conv1 / conv2 part of that launch reads and writes."""
+
     @staticmethod
-    def forward(ctx, z2, a2, idx2, w3, b3, wfc, bfc, packed, fused=None):
-        if fused is not None:  # (x, w1, b1, w2, b2, mean, std, in_scale, a1, idx1, do_pack): the whole forward
-            x, w1, b1, w2, b2, mean, std, in_scale, a1, idx1, do_pack = fused
-            logits, a3, idx3 = C.cn_forward_fused(x, w1, b1, w2, b2, w3, b3, wfc, bfc, mean, std, in_scale,
-                                                  a1, idx1, a2, idx2, packed, do_pack)
-        else:
-            logits, a3, idx3 = C.cn_conv3_fc_fwd(a2, packed, b3, bfc)
+    def forward(ctx, z2, a2, idx2, w3, b3, wfc, bfc, packed, fused):
+        x, w1, b1, w2, b2, mean, std, in_scale, a1, idx1, do_pack = fused
+        logits, a3, idx3 = C.cn_forward_fused(x, w1, b1, w2, b2, w3, b3, wfc, bfc, mean, std, in_scale,
+                                              a1, idx1, a2, idx2, packed, do_pack)
         ctx.mark_non_differentiable(a3, idx3)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(a2, idx2, a3, idx3, wfc, packed)
@@ -380,11 +333,6 @@ def _pack_state(conv1, conv2, conv3, fc1):
     return st, ws
 
 
-def pack_weights(conv1, conv2, conv3, fc1) -> torch.Tensor:
-    with torch.no_grad():
-        return C.cn_pack_weights(conv1.weight, conv2.weight, conv3.weight, fc1.weight)
-
-
 def convnet_forward(x: torch.Tensor, conv1, conv2, conv3, fc1) -> torch.Tensor:
     """Fused GPU forward of the reference ConvNet (ref/launch_dist.py:35-41).
 
@@ -396,28 +344,19 @@ def convnet_forward(x: torch.Tensor, conv1, conv2, conv3, fc1) -> torch.Tensor:
         x = x.float()
         mean, std, scale = 0.0, 1.0, 1.0
     x = x.contiguous()
-    fused = None
-    net = None
-    if _FUSE12 and _FUSED_FWD:
-        st, ws = _pack_state(conv1, conv2, conv3, fc1)
-        bufs = C.cn_forward_buffers(x)
-        if st.buf is None or st.buf.device != x.device:
-            st.buf = bufs[4]
-            st.invalidate()
-        bufs = (bufs[0], bufs[1], bufs[2], bufs[3], st.buf)
-        do_pack = st.consume(ws)  # False: the optimizer wrote these weights' fragments since the last forward
-        z2, a2, idx2, packed = _Conv12.apply(x, conv1.weight, conv1.bias, conv2.weight, conv2.bias,
-                                             conv3.weight.detach(), fc1.weight.detach(), mean, std, scale, bufs)
-        fused = (x, conv1.weight.detach(), conv1.bias.detach(), conv2.weight.detach(), conv2.bias.detach(),
-                 mean, std, scale, bufs[0], bufs[1], do_pack)
-        net = (x, bufs[1], bufs[0], conv1.weight, conv1.bias, conv2.weight, conv2.bias, (mean, std, scale))
-    elif _FUSE12:
-        z2, a2, idx2, packed = _Conv12.apply(x, conv1.weight, conv1.bias, conv2.weight, conv2.bias,
-                                             conv3.weight.detach(), fc1.weight.detach(), mean, std, scale)
-    else:
-        packed = pack_weights(conv1, conv2, conv3, fc1)
-        a1 = _Conv1.apply(x, conv1.weight, conv1.bias, packed, mean, std, scale)
-        z2, a2, idx2 = _Conv2.apply(a1, conv2.weight, conv2.bias, packed)
+    st, ws = _pack_state(conv1, conv2, conv3, fc1)
+    bufs = C.cn_forward_buffers(x)
+    if st.buf is None or st.buf.device != x.device:
+        st.buf = bufs[4]
+        st.invalidate()
+    bufs = (bufs[0], bufs[1], bufs[2], bufs[3], st.buf)
+    do_pack = st.consume(ws)  # False: the optimizer wrote these weights' fragments since the last forward
+    # _Conv12 adopts the (still empty) buffers; _Conv3FC's forward is the one launch that fills them
+    z2, a2, idx2, packed = _Conv12.apply(x, conv1.weight, conv1.bias, conv2.weight, conv2.bias, mean, std, scale,
+                                         bufs)
+    fused = (x, conv1.weight.detach(), conv1.bias.detach(), conv2.weight.detach(), conv2.bias.detach(),
+             mean, std, scale, bufs[0], bufs[1], do_pack)
+    net = (x, bufs[1], bufs[0], conv1.weight, conv1.bias, conv2.weight, conv2.bias, (mean, std, scale))
     logits, a3, idx3 = _Conv3FC.apply(z2, a2, idx2, conv3.weight, conv3.bias, fc1.weight, fc1.bias, packed,
                                       fused)
     if logits.requires_grad:

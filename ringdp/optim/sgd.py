@@ -16,7 +16,6 @@ captured hipGraph step picks up learning-rate schedule changes without re-captur
 """
 from __future__ import annotations
 
-import os
 from typing import Optional
 
 import torch
@@ -26,15 +25,9 @@ from .._native import C
 from ..utils import tracing as _tracing
 
 
-# RINGDP_CN_PACK_IN_SGD=0: the ConvNet forward packs its weights itself every step (A/B measurements)
-_PACK_IN_SGD = os.environ.get("RINGDP_CN_PACK_IN_SGD", "1") != "0"
-
-
 def _pack_target(params):
     """(state, flat offsets, weights) when the flat step can keep one model's packed weight fragments current
     (ringdp.ops.convnet.PackState: all 4 ConvNet weights in this group, their fragments built once)."""
-    if not _PACK_IN_SGD:
-        return None
     st, offs, ws = None, {}, {}
     for p in params:
         t = getattr(p, "_ringdp_pack", None)

@@ -269,6 +269,64 @@ def test_convnet_grads_vs_bf16_oracle(B):
     assert max(worst.values()) < 1e-1, worst
 
 
+_ORACLE_GRADS = {}
+
+
+def _oracle_case(B):
+    """Input, labels and the bf16-storage oracle's gradient of every parameter at batch B (seeded: the same
+    model and data as the tests build), computed once per batch and shared by the frozen sets below - a
+    parameter's gradient does not depend on which other parameters are frozen."""
+    if B not in _ORACLE_GRADS:
+        from ringdp.models import ConvNet
+
+        torch.manual_seed(0)
+        m = ConvNet().cuda()
+        g = torch.Generator(device="cuda").manual_seed(B)
+        x = torch.randint(0, 256, (B, 1, 28, 28), dtype=torch.uint8, device="cuda", generator=g)
+        y = torch.randint(0, 10, (B,), device="cuda", generator=g)
+        F.cross_entropy(_bf16_oracle_forward(m, x), y).backward()
+        _ORACLE_GRADS[B] = (x, y, {n: p.grad.clone() for n, p in m.named_parameters()})
+    return _ORACLE_GRADS[B]
+
+
+@pytest.mark.parametrize("frozen", [("conv1.weight", "conv1.bias"), ("conv2.weight",),
+                                    ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias")],
+                         ids=["conv1", "conv2w", "conv12"])
+@pytest.mark.parametrize("B", [100, 2049])
+def test_convnet_partially_frozen_grads_vs_bf16_oracle(B, frozen):
+    """A partially frozen ConvNet against the bf16-storage oracle, same gates as the unfrozen test over the
+    parameters that still require grad; frozen parameters end with no gradient.  Frozen conv1: conv2's
+    backward without da1; frozen conv2.weight: conv2's backward with da1, then conv1's weight gradient as
+    its own launch; conv1 and conv2 frozen: conv3's backward without an input gradient.  B = 100 takes the
+    4-wave conv3 backward with fc1 inside it, B = 2049 is the smallest batch of fc_bwd_kernel +
+    conv3_bwd8_kernel.  Each case runs through F.cross_entropy (_Conv3FC.backward) and through ringdp's
+    criterion, which must fall back from the whole-network node to _HeadCE."""
+    from ringdp.models import ConvNet
+    from ringdp.nn import CrossEntropyLoss
+
+    x, y, ref = _oracle_case(B)
+    torch.manual_seed(0)
+    m = ConvNet().cuda()
+    for n, p in m.named_parameters():
+        p.requires_grad_(n not in frozen)
+    for name, crit in (("aten", F.cross_entropy), ("ringdp", CrossEntropyLoss())):
+        m.zero_grad(set_to_none=True)
+        loss = crit(m(x), y)
+        if name == "ringdp":
+            assert type(loss.grad_fn).__name__ == "_HeadCEBackward", loss.grad_fn
+        loss.backward()
+        l2, worst = {}, {}
+        for n, p in m.named_parameters():
+            if n in frozen:
+                assert p.grad is None, n
+                continue
+            l2[n] = float((p.grad - ref[n]).norm() / ref[n].norm())
+            worst[n] = float((p.grad - ref[n]).abs().max() / ref[n].abs().max())
+        print(name, "l2", {k: f"{v:.1e}" for k, v in l2.items()}, "max", {k: f"{v:.1e}" for k, v in worst.items()})
+        assert max(l2.values()) < 2e-2, (name, l2)
+        assert max(worst.values()) < 1e-1, (name, worst)
+
+
 def test_convnet_bf16_trajectory_b4096():
     """200 SGD steps at B=4096 (the fc1-in-conv3 launch, the one-bucket regime) track the ATen fp32 loss."""
     from ringdp.models import ConvNet

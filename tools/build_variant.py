@@ -1,6 +1,11 @@
 """Build an A/B variant of the extension: one .hip source recompiled with extra -D flags, linked
 with the current in-tree objects into variants/<name>.so (run with RINGDP_EXT_PATH=variants/<name>.so,
-tools/gpu_ab_variants.sh).  usage: python tools/build_variant.py NAME csrc/kernels/x.hip -DFOO=1 ..."""
+tools/gpu_ab_variants.sh).  usage: python tools/build_variant.py NAME csrc/kernels/x.hip -DFOO=1 ...
+
+This is the only way to the diagnostic-build macros of csrc/kernels/convnet.hip: the timing-only phase
+ablations (wrong results) -DRINGDP_FF_ABLATE=n / -DRINGDP_C3_ABLATE=n / -DRINGDP_C12_ABLATE=n (bits at each
+macro) and the fused forward's phase stamps -DRINGDP_FF_STAMPS, e.g.
+  python tools/build_variant.py c3_nowgrad csrc/kernels/convnet.hip -DRINGDP_C3_ABLATE=4"""
 import importlib.util
 import sys
 from pathlib import Path
