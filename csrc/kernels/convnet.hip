@@ -324,6 +324,9 @@ __device__ __forceinline__ void glds16_async(const void* gsrc, void* lds_wave_ba
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(base), "v"(gsrc) : "memory");
 }
 __device__ __forceinline__ void c_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// the same with the wave's N newest vector-memory operations (stores issued after its DMAs) left in flight
+template <int N>
+__device__ __forceinline__ void c_dma_wait_but() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // The same copy from a wave-uniform base (SGPR pair) plus a 32-bit per-lane byte offset: the per-lane part of
 // an image's copy is the same for every image, so it is computed once and no 64-bit address math runs per copy.
@@ -1726,11 +1729,15 @@ __global__ __launch_bounds__(256, 1) void conv3_bwd_kernel(const bf16* __restric
 // ---- conv3 backward with 8-wave workgroups (batches above fc_in_c3_max_batch: the fc1 backward launch
 // leaves the compact gradient da3m).  One 512-thread workgroup per CU, in one of two roles:
 //   dgrad, wave-specialised: waves 0-3 hold the conv3 weights and only run image s's dgrad MFMAs and
-//     col2im (P[s&1] -> DA[s&1]); beside them waves 4-7 run the pool2 + ReLU backward of image s-1
-//     (DA, codes -> dz2), expand image s+1's compact gradient (stage -> P) and issue the LDS-DMA of
-//     later images.  One barrier per image: every buffer is written in one step and read in the next,
-//     so P, DA, the codes and the compact stage are double-buffered.  The 4-wave role above ran these
-//     phases one after the other, each behind a barrier of all four waves.
+//     col2im (P[s&1] -> DA[s&1]); beside them the helper waves 4-7, one per SIMD, expand image s+1's
+//     compact gradient (stage -> P) and run the pool2 + ReLU backward of image s-1 (DA, codes -> dz2), all
+//     256 lanes: 16 runs of 8 or 7 consecutive output positions x 16 channel quads (c3_pool2_bwd).  Wave 7,
+//     whose runs are the short ones, also issues the LDS-DMA of later images and waits for it with a vmcnt
+//     that leaves its own 7 dz2 stores in flight.  The helper waves run at raised priority: each shares
+//     its SIMD's issue port with an MFMA wave and is the one with the dependent chain.  One barrier per
+//     image: every buffer is written in one step and read in the next, so P, DA, the codes and the compact
+//     stage are double-buffered.  The 4-wave role above ran these phases one after the other, each behind
+//     a barrier of all four waves.
 //   wgrad: 8 waves cover the whole 128 x 576 dW3t of their image slice (36 tiles each, 2 x 4 waves), so
 //     an image is staged once (the 4-wave role needs a workgroup pair, each staging every image); image
 //     i+1's operands (compact gradient -> D, a2 -> X by LDS-DMA straight into the padded rows) are staged
@@ -1806,47 +1813,90 @@ __device__ __forceinline__ void a2_glds_rows(const bf16* __restrict__ a2, int b,
   if (voff != ~0u) glds16_sv(a2 + (int64_t)b * 6400, voff, X + k * 512);
 }
 
-// pool2 + ReLU backward of one image (threads t < 176: output row t >> 4, channel quad t & 15), as in
-// conv3_dgrad_role, from the swizzled da2 image
-__device__ __forceinline__ void c3_pool2_bwd(const float* DA, const uint8_t* AM, bf16* __restrict__ dz2, int b,
-                                             int t) {
-  const int gy = t >> 4, k = t & 15, gq = k * 4;
-  const int rowA = min(gy, 9), rowB = max(gy - 1, 0);
-  const int sA = gy <= 9 ? 0 : 4, sB = gy >= 1 ? 2 : 4;
-  auto masked_add = [](f32x4& g, uint32_t cw, int sh, const f32x4& d) {
-    const uint32_t m = (cw >> sh) & 0x01010101u;
-    g[0] = fmaf(d[0], ubyte_f32<0>(m), g[0]);
-    g[1] = fmaf(d[1], ubyte_f32<1>(m), g[1]);
-    g[2] = fmaf(d[2], ubyte_f32<2>(m), g[2]);
-    g[3] = fmaf(d[3], ubyte_f32<3>(m), g[3]);
+// pool2 + ReLU backward of one image on the 256 lanes of the four helper waves (conv3_dgrad_role's expressions,
+// from the swizzled da2 image).  The 121 output positions, row-major, are cut into 16 runs: runs 0-8 of 8
+// positions, runs 9-15 of 7 (9 * 8 + 7 * 7 = 121); a lane owns one channel quad of one run, so no lane forms
+// more than 8 outputs (a lane per output row formed 11, on 2.75 waves) and helper wave 3, which also issues
+// the LDS-DMA, forms 7.  A run keeps the walk along the row: an output's (y, x - 1) and (y - 1, x - 1) terms
+// are the da2 values and codes read for the output before it.  Everything that depends on the lane alone,
+// C3Pool2Map, is worked out once per workgroup, so the walk costs no address arithmetic per image.
+//   entry e = i + 1: what output i reads as its own column, (min(y, 9) | max(y - 1, 0), min(x, 9)); entry 0:
+//     the column before output 0's.  An output outside a row's 10 da2 columns or rows reads a clamped, valid
+//     address and masks the term with shift 4, a zero bit of every code byte (as the row clamps always did).
+//     Where a run crosses into the next row, output x = 0 multiplies the last row's column-9 values by 0.0:
+//     exact for finite gradients, which is all the kernels promise.
+//   lanes: the 16 lanes of one ds_read_b128 lane group (MI355X: {0-3,12-15,20-27}, {4-11,16-19,28-31} of each
+//     32) share a run and take its 16 channel quads, so every da2 read covers one 256-B position row: no bank
+//     conflict whatever the runs' columns are.
+struct C3Pool2Map {
+  int dst;              // bf16 offset of output 0 in the image's dz2
+  int daA[9], daB[9];   // float offsets into the da2 image, rows min(y, 9) and max(y - 1, 0)
+  int amA[9], amB[9];   // byte offsets into the pool2 codes, same rows
+  int sh[8][4];         // code bit of the window terms (y,x), (y,x-1), (y-1,x), (y-1,x-1), or 4
+  bool eight;           // the run has an 8th output
+};
+__device__ __forceinline__ void c3_pool2_map(int hwave, int lane, C3Pool2Map& m) {
+  const int q = (lane >> 2) & 7;
+  const int run = 4 * hwave + 2 * (lane >> 5) + (__builtin_popcount(q) & 1), k = (q >> 1) * 4 + (lane & 3);
+  const int p0 = run < 9 ? 8 * run : 7 * run + 9;
+  m.eight = run < 9;
+  m.dst = p0 * 64 + k * 4;
+  int gy = p0 / 11, x = p0 - 11 * gy;
+  auto entry = [&](int e, int xc) {
+    const int rowA = min(gy, 9), rowB = max(gy - 1, 0);
+    m.daA[e] = c3v_da(rowA * 10 + xc, xc, k);
+    m.daB[e] = c3v_da(rowB * 10 + xc, xc, k);
+    m.amA[e] = rowA * 640 + xc * 64 + k * 4;
+    m.amB[e] = rowB * 640 + xc * 64 + k * 4;
   };
-  const uint32_t* cA = reinterpret_cast<const uint32_t*>(AM + rowA * 640 + gq);
-  const uint32_t* cB = reinterpret_cast<const uint32_t*>(AM + rowB * 640 + gq);
-  bf16x4* dst = reinterpret_cast<bf16x4*>(dz2 + ((int64_t)b * 121 + gy * 11) * 64 + gq);
-  uint32_t pa = 0, pb = 0;
-  f32x4 qa = zero_f32x4(), qb = zero_f32x4();
+  entry(0, max(x - 1, 0));
 #pragma unroll
-  for (int x = 0; x < 11; ++x) {
-    uint32_t na = 0, nb2 = 0;
-    f32x4 ea = zero_f32x4(), eb = zero_f32x4();
-    if (x < 10) {
-      na = cA[x * 16];
-      nb2 = cB[x * 16];
-      ea = *reinterpret_cast<const f32x4*>(DA + c3v_da(rowA * 10 + x, x, k));
-      eb = *reinterpret_cast<const f32x4*>(DA + c3v_da(rowB * 10 + x, x, k));
+  for (int i = 0; i < 8; ++i) {
+    entry(i + 1, min(x, 9));
+    const int sA = gy <= 9 ? 0 : 4, sB = gy >= 1 ? 2 : 4;
+    m.sh[i][0] = x < 10 ? sA : 4;
+    m.sh[i][1] = x > 0 ? sA + 1 : 4;
+    m.sh[i][2] = x < 10 ? sB : 4;
+    m.sh[i][3] = x > 0 ? sB + 1 : 4;
+    if (++x == 11) {
+      x = 0;
+      ++gy;
     }
+  }
+}
+// dz2_img: the image's dz2.  The lane's stores: 8 (7 when !m.eight), one global_store_dwordx2 each.
+__device__ __forceinline__ void c3_pool2_bwd(const C3Pool2Map& m, const float* DA, const uint8_t* AM,
+                                             bf16* __restrict__ dz2_img) {
+  auto masked_add = [](f32x4& g, uint32_t cw, int sh, const f32x4& d) {
+    const uint32_t mk = (cw >> sh) & 0x01010101u;
+    g[0] = fmaf(d[0], ubyte_f32<0>(mk), g[0]);
+    g[1] = fmaf(d[1], ubyte_f32<1>(mk), g[1]);
+    g[2] = fmaf(d[2], ubyte_f32<2>(mk), g[2]);
+    g[3] = fmaf(d[3], ubyte_f32<3>(mk), g[3]);
+  };
+  auto code = [&](int off) { return *reinterpret_cast<const uint32_t*>(AM + off); };
+  auto da2 = [&](int off) { return *reinterpret_cast<const f32x4*>(DA + off); };
+  bf16x4* dst = reinterpret_cast<bf16x4*>(dz2_img + m.dst);
+  uint32_t pa = code(m.amA[0]), pb = code(m.amB[0]);
+  f32x4 qa = da2(m.daA[0]), qb = da2(m.daB[0]);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    if (i == 7 && !m.eight) break;
+    const uint32_t na = code(m.amA[i + 1]), nb2 = code(m.amB[i + 1]);
+    const f32x4 ea = da2(m.daA[i + 1]), eb = da2(m.daB[i + 1]);
     f32x4 g = zero_f32x4();
-    if (x < 10) masked_add(g, na, sA, ea);
-    if (x > 0) masked_add(g, pa, sA + 1, qa);
-    if (x < 10) masked_add(g, nb2, sB, eb);
-    if (x > 0) masked_add(g, pb, sB + 1, qb);
-    dst[x * 16] = bf16x4{(bf16)g[0], (bf16)g[1], (bf16)g[2], (bf16)g[3]};
+    masked_add(g, na, m.sh[i][0], ea);
+    masked_add(g, pa, m.sh[i][1], qa);
+    masked_add(g, nb2, m.sh[i][2], eb);
+    masked_add(g, pb, m.sh[i][3], qb);
+    dst[i * 16] = bf16x4{(bf16)g[0], (bf16)g[1], (bf16)g[2], (bf16)g[3]};
     pa = na;
     pb = nb2;
     qa = ea;
     qb = eb;
   }
 }
+constexpr int C3_POOL2_DMA_WAVE_STORES = 7;  // dz2 stores per image of helper wave 3 (runs 12-15)
 
 // RINGDP_C3_ABLATE (diagnostic builds only, tools/build_variant.py; timing only, wrong results): bit 0 skips the
 // pool2 backward of the 8-wave conv3 backward, bit 1 its dgrad MFMA phase, bit 2 its weight gradient.  A
@@ -1856,6 +1906,26 @@ __device__ __forceinline__ void c3_pool2_bwd(const float* DA, const uint8_t* AM,
 #define RINGDP_C3_ABLATE 0
 #endif
 constexpr int C3_ABLATE = RINGDP_C3_ABLATE;
+
+// RINGDP_C3_STAMPS (diagnostic builds only, tools/build_variant.py): lane 0 of every wave of the 8-wave dgrad
+// role records s_memtime at 4 phase points of steps [C3_ST_S0, C3_ST_S0 + 8) into LDS past C3V_LDS; workgroup
+// C3_ST_BLK prints them at the end, relative to wave 0's step start.  MFMA waves: 0 step start, 1 last MFMA
+// group issued, 2 col2im stored, 3 past the barrier; helper waves: 0 expand done, 1 pool2 done, 2 LDS-DMA
+// waited for, 3 past the barrier.
+#ifdef RINGDP_C3_STAMPS
+constexpr int C3_ST_S0 = 100, C3_ST_BLK = 5, C3_ST_BYTES = 8 * 8 * 4 * 8;
+#define C3_ST(k)                                                                                              \
+  do {                                                                                                        \
+    if (s >= C3_ST_S0 && s < C3_ST_S0 + 8 && (threadIdx.x & 63) == 0)                                         \
+      reinterpret_cast<unsigned long long*>(smem + C3V_LDS)[((threadIdx.x >> 6) * 8 + (s - C3_ST_S0)) * 4 + (k)] = \
+          __builtin_amdgcn_s_memtime();                                                                       \
+  } while (0)
+#else
+constexpr int C3_ST_BYTES = 0;
+#define C3_ST(k) \
+  do {           \
+  } while (0)
+#endif
 
 __device__ __forceinline__ void conv3_dgrad8_role(char* smem, const bf16* __restrict__ da3m,
                                                   const uint8_t* __restrict__ idx3, const uint8_t* __restrict__ idx2,
@@ -1893,6 +1963,7 @@ __device__ __forceinline__ void conv3_dgrad8_role(char* smem, const bf16* __rest
     lds_barrier();  // [B0] zero rows
     lds_barrier();  // [B1] image 0 expanded
     for (int s = 0; s <= n; ++s) {
+      C3_ST(0);
       if (s < n && !(C3_ABLATE & 2)) {
         const bf16* P = Pb(s & 1);
         float* DA = DAb(s & 1);
@@ -1922,6 +1993,7 @@ __device__ __forceinline__ void conv3_dgrad8_role(char* smem, const bf16* __rest
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx) acc[kx] = mfma16x16x32(aw[(3 * ky + kx) * 4 + ks], bcur[ks], acc[kx]);
           if (g + 1 < NG && gmt(g + 1) == mt) continue;
+          if (g + 1 == NG) C3_ST(1);
           // col2im along the row in registers: da2(x) = acc0(x) + acc1(x-1) + acc2(x-2), the shifted terms
           // by DPP row shifts inside each 16-lane group (= 2 dz3 rows x 8 columns; a term that would cross
           // into the next row is zeroed at its source lane); column 8 = acc1(7) + acc2(6), column 9 =
@@ -1940,13 +2012,23 @@ __device__ __forceinline__ void conv3_dgrad8_role(char* smem, const bf16* __rest
           }
         }
       }
+      C3_ST(2);
       lds_barrier();
+      C3_ST(3);
     }
   } else {
-    // ---- VALU waves: thread vt of 256; wave 7 issues every LDS-DMA (it has no pool2 items, so its
-    // vmcnt covers exactly its DMAs)
+    // ---- VALU waves: thread vt of 256; wave 7 issues every LDS-DMA: it has the fewest pool2 outputs, and
+    // its dz2 stores of a step all follow that step's DMAs, so a vmcnt that leaves exactly those stores out
+    // (memory operations of one wave retire in order) waits for the DMAs alone
     const int vt = tid - 256;
     const bool dma = wave == 7;
+    C3Pool2Map pmap;
+    c3_pool2_map(wave - 4, lane, pmap);
+    // The helper waves go first at their SIMD's issue port.  An MFMA wave keeps the port busy with long
+    // matrix instructions that it can issue back to back; at equal priority the helper wave beside it got
+    // what was left, trailed its MFMA wave by 1200 cycles per image and set the step (stamps:
+    // profiles/r07/c3_dgrad/stamps.md).  Ahead of it, both finish together, 5 % sooner.
+    __builtin_amdgcn_s_setprio(2);
     auto row_ptr = [&](bf16* P) {
       return [P](int r) {
         const int w = r >> 2, i = r & 3;
@@ -1982,11 +2064,29 @@ __device__ __forceinline__ void conv3_dgrad8_role(char* smem, const bf16* __rest
         c3s_pre(Sb((s + 1) & 1), vt, pre);
         c3_expand(pre, vt, row_ptr(Pb((s + 1) & 1)));
       }
-      if (s >= 1 && vt < 176 && !(C3_ABLATE & 1)) c3_pool2_bwd(DAb((s - 1) & 1), AMb((s - 1) & 1), dz2, b_first + (s - 1) * b_step, vt);
+      C3_ST(0);
+      const bool pool = s >= 1 && !(C3_ABLATE & 1);
+      if (pool) {
+        // the buffer as a constant: the precomputed offsets then meet it in the reads' immediate fields
+        bf16* dz2_img = dz2 + (int64_t)(b_first + (s - 1) * b_step) * (121 * 64);
+        if ((s - 1) & 1)
+          c3_pool2_bwd(pmap, DAb(1), AMb(1), dz2_img);
+        else
+          c3_pool2_bwd(pmap, DAb(0), AMb(0), dz2_img);
+      }
+      C3_ST(1);
       // (issuing image s+1's codes a step earlier and leaving them in flight measured slower)
-      if (dma) c_dma_wait();
+      if (dma) {
+        if (pool)
+          c_dma_wait_but<C3_POOL2_DMA_WAVE_STORES>();
+        else
+          c_dma_wait();
+      }
+      C3_ST(2);
       lds_barrier();
+      C3_ST(3);
     }
+    __builtin_amdgcn_s_setprio(0);
   }
 }
 
@@ -2106,10 +2206,23 @@ __global__ __launch_bounds__(512, 1) void conv3_bwd8_kernel(const bf16* __restri
                                                            const bf16* __restrict__ packed, bf16* __restrict__ dz2,
                                                            int B, float* __restrict__ slabs, int n_wgrad, int n_dgrad,
                                                            int b_dgrad) {
-  __shared__ __attribute__((aligned(16))) char smem[C3V_LDS];
+  __shared__ __attribute__((aligned(16))) char smem[C3V_LDS + C3_ST_BYTES];
   const int blk = blockIdx.x;
   if (blk < n_dgrad) {
     conv3_dgrad8_role(smem, da3m, idx3, idx2, packed, dz2, blk, b_dgrad, n_dgrad);
+#ifdef RINGDP_C3_STAMPS
+    __syncthreads();
+    if (blk == C3_ST_BLK && threadIdx.x == 0 && (b_dgrad - blk) / n_dgrad > C3_ST_S0 + 8) {
+      const unsigned long long* st = reinterpret_cast<const unsigned long long*>(smem + C3V_LDS);
+      for (int w = 0; w < 8; ++w)
+        for (int k = 0; k < 8; ++k) {
+          const unsigned long long* r = st + (w * 8 + k) * 4;
+          const unsigned long long t0 = st[k * 4];  // wave 0's step start
+          printf("C3ST w%d s%d %lld %lld %lld %lld\n", w, k, (long long)(r[0] - t0), (long long)(r[1] - t0),
+                 (long long)(r[2] - t0), (long long)(r[3] - t0));
+        }
+    }
+#endif
     return;
   }
   const int w = blk - n_dgrad;
@@ -3275,14 +3388,14 @@ static bool c3_v3(int B) { return B > fc_in_c3_max_batch(); }
 static void c3_split(int B, bool dgrad, int& nd, int& ws) {
   if (c3_v3(B)) {  // one 512-thread workgroup per CU; ws = wgrad slices, one workgroup each
     const int cus = num_cus();
-    if (!dgrad) {
-      nd = 0;
-      ws = clampi(cdiv(B, 8), 1, cus);
-      return;
-    }
     static const double frac = split_frac("RINGDP_C3_DGRAD_FRAC", 0.55);
     nd = clampi(((int)(frac * cus) + 4) / 8 * 8, 8, cus - 8);  // multiples of 8: see conv3_wgrad8_role
     ws = clampi(cdiv(B, 8), 1, cus - nd);
+    // Without a data gradient the same slices, on as many workgroups, and no dgrad workgroups: a slice is a
+    // slab and fixes the fp32 order in which dW3 and db3 are summed, so the weight gradients of a call do not
+    // depend on whether it also asks for dz2 (byte-equal; one slice per CU would sum in another order).  The
+    // CUs the dgrad role would have had stay idle in such a call.
+    if (!dgrad) nd = 0;
     return;
   }
   // 256-thread workgroups, two per CU; ws = image slices, each served by a pair of workgroups
@@ -3301,13 +3414,16 @@ static void c3_split(int B, bool dgrad, int& nd, int& ws) {
 
 // Images [0, result) of the conv3 data gradient run on the dgrad workgroups, the rest on the wgrad
 // workgroups after their weight-gradient slice (RINGDP_C3_STEAL = that share; large batches only, where
-// each dgrad workgroup has many images).  0.07 (was 0.1): B=65536 step 3.304-3.315 -> 3.259-3.292 ms, three
-// passes each of 0.06 / 0.07 / 0.08 all ahead of 0.1, 0.0 behind it (profiles/r06/c3_steal_sweep.txt).
+// each dgrad workgroup has many images).  0.04 since the dgrad role's image takes 10 % fewer cycles (pool2
+// backward on all four helper waves, helper waves ahead at the issue port): conv3 + fc1 backward at B=65536,
+// three passes each, 1166-1175 us at 0.04, 1172-1178 at 0.05, 1178-1183 at 0.03, 1191-1198 at 0.07, the
+// parent kernel 1209-1215 (profiles/r07/c3_dgrad/README.md).  0.07 had replaced 0.1 for the old role
+// (profiles/r06/c3_steal_sweep.txt).
 static int c3_dgrad_images(int B, int nd) {
   static const double steal = [] {
     const char* v = getenv("RINGDP_C3_STEAL");
-    const double f = v ? atof(v) : 0.07;
-    return f >= 0.0 && f < 0.9 ? f : 0.07;
+    const double f = v ? atof(v) : 0.04;
+    return f >= 0.0 && f < 0.9 ? f : 0.04;
   }();
   if (nd <= 0 || B < 32 * nd) return B;
   return B - (int)(steal * B);
