@@ -2764,11 +2764,14 @@ __global__ __launch_bounds__(512) void conv12_bwd_kernel(const void* __restrict_
 // scheme; batches above fc_in_c3_max_batch).  One 512-thread workgroup per CU:
 //   dgrad: waves 0-3 run conv2's data gradient of image s (both 16-channel n-tiles per wave, so every
 //     A-fragment read feeds 2 MFMAs: half the LDS reads of conv12_dgrad_role) into da1 O[s&1]; beside them
-//     waves 4-7 run conv1's weight gradient of image s-1 (from O[(s-1)&1]) and stage image s+1 (dz2 ->
-//     P, input copies, pool1 codes; registers loaded one step ahead).  One barrier per image.  The
-//     input copies and codes of image s-1 are still read while image s+1 is staged: three of those.
+//     waves 4-7 stage image s+1 (dz2 -> P, input copies, pool1 codes; registers loaded two steps ahead).
+//     conv1's weight gradient of image s-1 (from O[(s-1)&1]) is shared by all 8 waves: 16 of its 26 k-steps
+//     on waves 4-7, 10 on waves 0-3 after their conv2 phase (profiles/r07/c12_bwd/README.md: the MFMA waves
+//     had waited 2000 of 5400 cycles per image at the barrier).  One barrier per image.  The input copies
+//     and codes of image s-1 are still read while image s+1 is staged: three of those.
 //   wgrad: conv2's weight gradient, 8 waves each 2 co tiles x 4-5 n-tiles (14 tr16 reads per 10 MFMAs per
-//     k-step instead of 20 per 9), image i+1 staged from registers while image i's MFMAs run.
+//     k-step instead of 20 per 9), image i+2 staged from registers while image i's MFMAs run (waves 0-3
+//     before their k-steps, waves 4-7 after theirs).
 constexpr int C12V_DG = 2 * (C2D_P + C12_O) + 3 * (C12_XS + C1I_IMG);  // 155104
 constexpr int C12V_WG = 3 * (C2W_D + C2W_X);                           // 108144
 constexpr int C12V_LDS = C12V_DG > C12V_WG ? C12V_DG : C12V_WG;
@@ -2785,6 +2788,27 @@ static_assert(C12V_LDS <= 160 * 1024 && C1I_IMG % 16 == 0, "conv12 backward (8-w
 #define RINGDP_C12_ABLATE 0
 #endif
 constexpr int C12_ABLATE = RINGDP_C12_ABLATE;
+
+// RINGDP_C12_STAMPS (diagnostic builds only, tools/build_variant.py): lane 0 of every wave records s_memtime at
+// up to 4 phase points of steps [C12_ST_S0, C12_ST_S0 + 8) into LDS past C12V_LDS; dgrad workgroup C12_ST_BLK
+// ("C12ST d") and wgrad slice C12_ST_BLK ("C12ST w") print them at the end, relative to their wave 0's first
+// stamp.  dgrad MFMA waves: 0 step start (just past the previous barrier), 1 last MFMA issued, 2 da1 stored, 3
+// conv1 share done; dgrad helper waves: 0 stage done, 1 loads issued, 2 conv1 share done, 3 past the barrier;
+// wgrad waves: 0 stage done, 1 last k-step done, 2 past the barrier.
+#ifdef RINGDP_C12_STAMPS
+constexpr int C12_ST_S0 = 100, C12_ST_BLK = 5, C12_ST_BYTES = 8 * 8 * 4 * 8;
+#define C12_ST(s, k)                                                                                              \
+  do {                                                                                                            \
+    if ((s) >= C12_ST_S0 && (s) < C12_ST_S0 + 8 && (threadIdx.x & 63) == 0)                                       \
+      reinterpret_cast<unsigned long long*>(smem + C12V_LDS)[((threadIdx.x >> 6) * 8 + ((s) - C12_ST_S0)) * 4 + (k)] = \
+          __builtin_amdgcn_s_memtime();                                                                           \
+  } while (0)
+#else
+constexpr int C12_ST_BYTES = 0;
+#define C12_ST(s, k) \
+  do {               \
+  } while (0)
+#endif
 
 template <bool U8>
 __device__ __forceinline__ void conv12_dgrad8_role(char* smem, const void* __restrict__ xin,
@@ -2804,6 +2828,81 @@ __device__ __forceinline__ void conv12_dgrad8_role(char* smem, const void* __res
     reinterpret_cast<bf16x8*>(smem)[c] = zero_bf16x8();
   __syncthreads();
   if ((ablate & 8) && wave >= 4) __builtin_amdgcn_s_setprio(1);
+  // ---- conv1's weight gradient of one image, 26 k-steps (window row py = ks >> 1, row half dy = ks & 1) shared
+  // by all 8 waves: the MFMA waves end their conv2 phase well before the helper waves end theirs, so MFMA
+  // waves 0-2 take C12_KM k-steps each and wave 3 (2 m-tiles) C12_KM3; the helper waves share the first C12_KH
+  // (vw, vw + 4, ..).  Every wave sums its own k-steps over all images; the 8 partial sums are combined at the
+  // end in a fixed order.  All LDS addresses are 32-bit byte offsets from smem: a per-lane part formed once and
+  // scalar per-image and per-k-step parts.  (Formed from pointers they compiled to 64-bit multiply-adds whose
+  // undefined high halves shared registers with the global loads in flight, and the loop waited for those.)
+  constexpr int C12_KM = 2, C12_KM3 = 4, C12_KH = 26 - 3 * C12_KM - C12_KM3;
+  static_assert(C12_KH >= 4 && C12_KM >= 0 && C12_KM3 >= 0, "conv1 k-step partition");
+  const int k0 = wave < 4 ? C12_KH + wave * C12_KM : wave - 4, kst = wave < 4 ? 1 : 4;
+  const int kcnt = wave < 3 ? C12_KM : wave == 3 ? C12_KM3 : (C12_KH - (wave - 4) + 3) / 4;
+  const int i16 = lane & 15, g = lane >> 4, q = i16 >> 2, p = i16 & 3;
+  const int t1 = 16 + i16;
+  const int xoff0 = (i16 % 5) * C1W_CS + (i16 / 5) * C1W_RS + 8 * g;
+  const int xoff1 = t1 < 25 ? (t1 % 5) * C1W_CS + (t1 / 5) * C1W_RS + 8 * g : 0;
+  const uint32_t b1fill = t1 == 25 ? 0x3f803f80u : 0u;
+  f32x4 acc1[2][2];
+#pragma unroll
+  for (int m = 0; m < 2; ++m) acc1[m][0] = acc1[m][1] = zero_f32x4();
+  const int o_lane = ((4 * g + q) * C2_ORS + 4 * p) * 2;
+  const int c_lane = (i16 >> 1) * 16 + 4 * g, csh_lane = 4 * (i16 & 1);
+  struct C1F {
+    uint2 d[2];
+    uint32_t cu[2];
+    bf16x8 b0, b1;
+  };
+  // oimg / ximg / cimg: byte offsets of the image's da1, input copies and codes
+  auto c1_read = [&](int ks, int oimg, int ximg, int cimg, C1F& f) {
+    const int py = ks >> 1;
+    int oa = oimg + py * (13 * C2_ORS * 2) + o_lane, ca = cimg + py * 256 + c_lane;
+    int x0 = ximg + ks * (C1W_RS * 2) + xoff0 * 2, x1 = ximg + ks * (C1W_RS * 2) + xoff1 * 2;
+    asm("" : "+v"(oa), "+v"(ca), "+v"(x0), "+v"(x1));  // one VGPR address each; m is an immediate offset
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      f.d[m] = __builtin_bit_cast(uint2, lds_read_tr16(reinterpret_cast<const bf16*>(smem + oa) + m * 16));
+      f.cu[m] = *reinterpret_cast<const uint32_t*>(smem + ca + m * 128);
+    }
+    f.b0 = *reinterpret_cast<const bf16x8*>(smem + x0);
+    f.b1 = *reinterpret_cast<const bf16x8*>(smem + x1);
+  };
+  auto c1_mma = [&](int ks, const C1F& f) {
+    bf16x8 A[2];
+    const int csh = csh_lane + 2 * (ks & 1);
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      const uint2 d = f.d[m];
+      const uint32_t cu = f.cu[m];
+      uint32_t pr[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const uint32_t dv = e & 1 ? (e < 2 ? d.x : d.y) >> 16 : (e < 2 ? d.x : d.y) & 0xffffu;
+        const uint32_t sel = __builtin_amdgcn_ubfe(cu, 8 * e + csh, 2);
+        pr[e] = dv * ((sel * 0x8001u) & 0x10001u);
+      }
+      A[m] = __builtin_bit_cast(bf16x8, make_uint4(pr[0], pr[1], pr[2], pr[3]));
+    }
+    bf16x8 B1 = f.b1;
+    if (t1 >= 25) B1 = __builtin_bit_cast(bf16x8, make_uint4(b1fill, b1fill, b1fill, b1fill));
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      acc1[m][0] = mfma16x16x32(A[m], f.b0, acc1[m][0]);
+      acc1[m][1] = mfma16x16x32(A[m], B1, acc1[m][1]);
+    }
+  };
+  // this wave's k-steps of image j (its da1 is complete: call it in step j + 1)
+  auto c1_image = [&](int j) {
+    const int oimg = 2 * C2D_P + (j & 1) * C12_O;
+    const int ximg = 2 * (C2D_P + C12_O) + (j % 3) * C12_XS;
+    const int cimg = 2 * (C2D_P + C12_O) + 3 * C12_XS + (j % 3) * C1I_IMG;
+    for (int i = 0, ks = k0; i < kcnt; ++i, ks += kst) {
+      C1F f;
+      c1_read(ks, oimg, ximg, cimg, f);
+      c1_mma(ks, f);
+    }
+  };
   if (wave < 4) {
     // ---- MFMA waves: m-tiles wave, wave + 4, wave + 8 (< 11), both n-tiles.  Weights are the A operand
     // (the B-fragment pack read as A: the same lane -> (channel, k) map), so a lane's 4 results are 4
@@ -2823,7 +2922,7 @@ __device__ __forceinline__ void conv12_dgrad8_role(char* smem, const void* __res
       opos[k] = mm;
       base[k] = mm == 255 ? 0 : (mm / 13) * C2_PW + mm % 13;
     }
-    auto phase = [&](auto nk_c, const bf16* P, bf16* O) {
+    auto phase = [&](auto nk_c, const bf16* P, bf16* O, int s) {
       constexpr int NK = decltype(nk_c)::value;
       f32x4 acc[NK][2];
 #pragma unroll
@@ -2839,6 +2938,7 @@ __device__ __forceinline__ void conv12_dgrad8_role(char* smem, const void* __res
           acc[k][1] = mfma16x16x32(bw[1][ks], a, acc[k][1]);
         }
       }
+      C12_ST(s, 1);
 #pragma unroll
       for (int k = 0; k < NK; ++k) {
         if (opos[k] < 169) {
@@ -2851,33 +2951,24 @@ __device__ __forceinline__ void conv12_dgrad8_role(char* smem, const void* __res
     };
     lds_barrier();  // [B1] image 0 staged
     for (int s = 0; s <= n; ++s) {
+      C12_ST(s, 0);
       if (s < n && !(ablate & 2)) {
         if (wave < 3)
-          phase(std::integral_constant<int, 3>{}, Pb(s & 1), Ob(s & 1));
+          phase(std::integral_constant<int, 3>{}, Pb(s & 1), Ob(s & 1), s);
         else
-          phase(std::integral_constant<int, 2>{}, Pb(s & 1), Ob(s & 1));
+          phase(std::integral_constant<int, 2>{}, Pb(s & 1), Ob(s & 1), s);
       }
+      C12_ST(s, 2);
+      if (s >= 1 && !(ablate & 1)) c1_image(s - 1);
+      C12_ST(s, 3);
       lds_barrier();
     }
-    __syncthreads();  // [R0] the V waves' conv1 reduction reuses P
-    __syncthreads();  // [R1]
   } else {
     // ---- conv1-wgrad / staging waves: thread vt of 256
-    const int vt = tid - 256, vw = wave - 4;
-    const int i16 = lane & 15, g = lane >> 4, q = i16 >> 2, p = i16 & 3;
-    const int t1 = 16 + i16;
-    const int xoff0 = (i16 % 5) * C1W_CS + (i16 / 5) * C1W_RS + 8 * g;
-    const int xoff1 = t1 < 25 ? (t1 % 5) * C1W_CS + (t1 / 5) * C1W_RS + 8 * g : 0;
-    const uint32_t b1fill = t1 == 25 ? 0x3f803f80u : 0u;
-    const int dy = vw & 1;  // k-steps vw, vw + 4, ...: one window-row half per wave
-    f32x4 acc1[2][2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc1[m][0] = acc1[m][1] = zero_f32x4();
-    // the next images' inputs in registers, two sets: image j's set is j & 1, loaded two steps before it is
-    // staged (one step of latency hiding was not enough: staging alone ran at the per-CU latency bound)
+    const int vt = tid - 256;
     // the next images' inputs in registers, two sets: image j's set is j & 1, loaded two steps before it is
     // staged (one step of latency hiding was not enough: staging alone ran at the per-CU latency bound).
-    // (Staging dz2 from the MFMA waves instead measured 935 -> 1024 us: they are the critical path.)
+    // (Staging dz2 from the MFMA waves instead measured 935 -> 1024 us in round 5.)
     struct Regs {
       bf16x8 pz[4];
       uint4 pc;
@@ -2906,33 +2997,6 @@ __device__ __forceinline__ void conv12_dgrad8_role(char* smem, const void* __res
       if (vt < C1I_IMG / 16) reinterpret_cast<uint4*>(Cb(k3))[vt] = r.pc;
       c1_store<U8, 5, C1W_RS, C1W_CS>(Xb(k3), vt, r.xu, r.xf, mean, inv_std, in_scale);
     };
-    auto c1_step = [&](int ks, const bf16* O, const bf16* xs, const uint8_t* CB) {
-      const int py = ks >> 1;
-      bf16x8 A[2];
-#pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        const uint2 d = __builtin_bit_cast(uint2, lds_read_tr16(O + (py * 13 + 4 * g + q) * C2_ORS + m * 16 + 4 * p));
-        const int co = m * 16 + i16;
-        const uint32_t cu = *reinterpret_cast<const uint32_t*>(CB + py * 256 + (co >> 1) * 16 + 4 * g);
-        const int csh = 4 * (co & 1) + 2 * dy;
-        uint32_t pr[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const uint32_t dv = e & 1 ? (e < 2 ? d.x : d.y) >> 16 : (e < 2 ? d.x : d.y) & 0xffffu;
-          const uint32_t sel = __builtin_amdgcn_ubfe(cu, 8 * e + csh, 2);
-          pr[e] = dv * ((sel * 0x8001u) & 0x10001u);
-        }
-        A[m] = __builtin_bit_cast(bf16x8, make_uint4(pr[0], pr[1], pr[2], pr[3]));
-      }
-      const bf16x8 B0 = *reinterpret_cast<const bf16x8*>(xs + xoff0 + ks * C1W_RS);
-      bf16x8 B1 = *reinterpret_cast<const bf16x8*>(xs + xoff1 + ks * C1W_RS);
-      if (t1 >= 25) B1 = __builtin_bit_cast(bf16x8, make_uint4(b1fill, b1fill, b1fill, b1fill));
-#pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        acc1[m][0] = mfma16x16x32(A[m], B0, acc1[m][0]);
-        acc1[m][1] = mfma16x16x32(A[m], B1, acc1[m][1]);
-      }
-    };
     if (n > 0) {
       load(r0, block);
       stage(r0, 0, 0);
@@ -2940,37 +3004,39 @@ __device__ __forceinline__ void conv12_dgrad8_role(char* smem, const void* __res
       if (n > 2) load(r0, block + 2 * nblocks);
     }
     lds_barrier();  // [B1]
-    // step s: stage image s+1 (its set (s+1) & 1), refill that set with image s+3, conv1 wgrad of image s-1
+    // step s: stage image s+1 (its set (s+1) & 1), refill that set with image s+3, this wave's share of the
+    // conv1 wgrad of image s-1
     auto step = [&](int s, Regs& rs) {
       if (s + 1 < n) {
         stage(rs, (s + 1) & 1, (s + 1) % 3);
+        C12_ST(s, 0);
         if (s + 3 < n) load(rs, block + (s + 3) * nblocks);
       }
-      if (s >= 1 && !(ablate & 1)) {
-        const bf16* O = Ob((s - 1) & 1);
-        const bf16* xs = Xb((s - 1) % 3);
-        const uint8_t* CB = Cb((s - 1) % 3);
-        for (int ks = vw; ks < 26; ks += 4) c1_step(ks, O, xs, CB);
-      }
+      C12_ST(s, 1);
+      if (s >= 1 && !(ablate & 1)) c1_image(s - 1);
+      C12_ST(s, 2);
       lds_barrier();
+      C12_ST(s, 3);
     };
     for (int s = 0; s <= n; s += 2) {  // unrolled by 2: register sets are not indexable
       step(s, r1);
       if (s + 1 <= n) step(s + 1, r0);
     }
-    // combine the 4 K-groups in a fixed order (deterministic) and write this workgroup's conv1 slab
-    __syncthreads();  // [R0]
-    float* red = reinterpret_cast<float*>(smem);  // [vw][tile][lane][4]: 16 KiB over P
+  }
+  // combine the 8 waves' partial sums in a fixed order (deterministic) and write this workgroup's conv1 slab
+  __syncthreads();  // [R0] P is free
+  float* red = reinterpret_cast<float*>(smem);  // [wave][tile][lane][4]: 32 KiB over P
 #pragma unroll
-    for (int m = 0; m < 2; ++m)
+  for (int m = 0; m < 2; ++m)
 #pragma unroll
-      for (int nn = 0; nn < 2; ++nn)
-        *reinterpret_cast<f32x4*>(red + ((vw * 4 + m * 2 + nn) * 64 + lane) * 4) = acc1[m][nn];
-    __syncthreads();  // [R1]
-    const int tile = vw;
+    for (int nn = 0; nn < 2; ++nn)
+      *reinterpret_cast<f32x4*>(red + ((wave * 4 + m * 2 + nn) * 64 + lane) * 4) = acc1[m][nn];
+  __syncthreads();  // [R1]
+  if (wave >= 4) {
+    const int tile = wave - 4;
     f32x4 sum = *reinterpret_cast<const f32x4*>(red + (tile * 64 + lane) * 4);
 #pragma unroll
-    for (int w = 1; w < 4; ++w) sum += *reinterpret_cast<const f32x4*>(red + ((w * 4 + tile) * 64 + lane) * 4);
+    for (int w = 1; w < 8; ++w) sum += *reinterpret_cast<const f32x4*>(red + ((w * 4 + tile) * 64 + lane) * 4);
     float* slab = slabs1 + (int64_t)block * C1_WSLAB;
     const int tap = (tile & 1) * 16 + i16;
 #pragma unroll
@@ -3062,10 +3128,15 @@ __device__ __forceinline__ void conv2_wgrad8_role(char* smem, const bf16* __rest
     constexpr int NJ = H == 0 ? 5 : 4;
     auto image = [&](int i, Regs& rs) {
       const int cur = i % 3;
-      if (i + 2 < n) {  // image i+2 (set rs) into the buffers image i-1 used; rs refilled with image i+4
+      // image i+2 (set rs) into the buffers image i-1 used; rs refilled with image i+4.  Waves 0-3 do it before
+      // their k-steps and waves 4-7 after theirs: waves w and w + 4 share a SIMD, so one of the two has MFMAs
+      // to issue while the other writes LDS and forms load addresses.
+      const bool early = wave < 4;
+      if (early && i + 2 < n) {
         stage(rs, (i + 2) % 3);
         if (i + 4 < n) load(rs, img(i + 4));
       }
+      C12_ST(i, 0);
       const int xb = (int)(Xb(cur) - reinterpret_cast<const bf16*>(smem)) + 16 * half + 4 * p;
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
@@ -3100,7 +3171,13 @@ __device__ __forceinline__ void conv2_wgrad8_role(char* smem, const bf16* __rest
           for (int m = 0; m < 2; ++m) accb[m] = mfma16x16x32((ks & 1) ? afn[m] : af[m], onesf, accb[m]);
         }
       }
+      C12_ST(i, 1);
+      if (!early && i + 2 < n) {
+        stage(rs, (i + 2) % 3);
+        if (i + 4 < n) load(rs, img(i + 4));
+      }
       lds_barrier();
+      C12_ST(i, 2);
     };
     for (int i = 0; i < n; i += 2) {  // unrolled by 2: register sets are not indexable
       image(i, r0);
@@ -3136,12 +3213,27 @@ __global__ __launch_bounds__(512, 1) void conv12_bwd8_kernel(const void* __restr
                                                             float inv_std, float in_scale,
                                                             float* __restrict__ slabs2, int nslices,
                                                             float* __restrict__ slabs1, int n_dgrad, int ablate) {
-  __shared__ __attribute__((aligned(16))) char smem[C12V_LDS];
+  __shared__ __attribute__((aligned(16))) char smem[C12V_LDS + C12_ST_BYTES];
   if ((int)blockIdx.x < n_dgrad)
     conv12_dgrad8_role<U8>(smem, xin, idx1, dz2, packed, B, blockIdx.x, n_dgrad, mean, inv_std, in_scale, slabs1,
                            ablate);
   else if (!(ablate & 4))
     conv2_wgrad8_role(smem, a1, dz2, slabs2, B, nslices, blockIdx.x - n_dgrad);
+#ifdef RINGDP_C12_STAMPS
+  __syncthreads();
+  const bool dg = (int)blockIdx.x < n_dgrad;
+  const int blk = dg ? blockIdx.x : blockIdx.x - n_dgrad, nb = dg ? n_dgrad : nslices;
+  if (blk == C12_ST_BLK && threadIdx.x == 0 && (B - blk) / nb > C12_ST_S0 + 8) {
+    const unsigned long long* st = reinterpret_cast<const unsigned long long*>(smem + C12V_LDS);
+    const unsigned long long t0 = st[0];  // wave 0's first stamp
+    for (int w = 0; w < 8; ++w)
+      for (int k = 0; k < 8; ++k) {
+        const unsigned long long* r = st + (w * 8 + k) * 4;
+        printf("C12ST %c w%d s%d %lld %lld %lld %lld\n", dg ? 'd' : 'w', w, k, (long long)(r[0] - t0),
+               (long long)(r[1] - t0), (long long)(r[2] - t0), dg ? (long long)(r[3] - t0) : 0ll);
+      }
+  }
+#endif
 }
 
 // ================================================================== fixed-order slab reductions
@@ -3451,7 +3543,7 @@ static bool c12_v3(int B) { return B > fc_in_c3_max_batch(); }
 static void c12_split(int B, int& nd, int& ws) {
   const int cus = num_cus();
   if (c12_v3(B)) {
-    static const double frac3 = split_frac("RINGDP_C12_DGRAD_FRAC", 0.65);
+    static const double frac3 = split_frac("RINGDP_C12_DGRAD_FRAC", 0.59);
     nd = clampi(((int)(frac3 * cus) + 4) / 8 * 8, 8, cus - 8);  // multiples of 8: see conv2_wgrad8_role
     ws = clampi(cdiv(B, 8), 1, cus - nd);
     return;

@@ -4,8 +4,8 @@ tools/gpu_ab_variants.sh).  usage: python tools/build_variant.py NAME csrc/kerne
 
 This is the only way to the diagnostic-build macros of csrc/kernels/convnet.hip: the timing-only phase
 ablations (wrong results) -DRINGDP_FF_ABLATE=n / -DRINGDP_C3_ABLATE=n / -DRINGDP_C12_ABLATE=n (bits at each
-macro), the fused forward's phase stamps -DRINGDP_FF_STAMPS and those of the 8-wave conv3 dgrad role
--DRINGDP_C3_STAMPS, e.g.
+macro), the fused forward's phase stamps -DRINGDP_FF_STAMPS, those of the 8-wave conv3 dgrad role
+-DRINGDP_C3_STAMPS and those of both roles of the 8-wave conv12 backward -DRINGDP_C12_STAMPS, e.g.
   python tools/build_variant.py c3_nowgrad csrc/kernels/convnet.hip -DRINGDP_C3_ABLATE=4"""
 import importlib.util
 import sys
