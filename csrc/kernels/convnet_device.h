@@ -1,0 +1,91 @@
+// bf16 ConvNet (design: convnet.hip): what both convnet.hip and convnet_bwd3.hip use on the device - the packed-weight
+// layout, the LDS-DMA copies, the a2 staging and the phase-stamp macro.
+#pragma once
+
+#include "device_common.h"
+
+namespace ringdp::kern {
+using namespace ringdp::dev;
+namespace {
+
+// ------------------------------------------------------------------ packed weight layout
+// bf16 element offsets inside the packed buffer.  Fragment order: [n-tile][k-step][lane][8].
+constexpr int P1_OFF = 0, P1_N = 2 * 2 * 512;                   // conv1 fwd   (K = kh*8 + kw, 2 k-steps)
+constexpr int P2F_OFF = P1_OFF + P1_N, P2F_N = 4 * 9 * 512;     // conv2 fwd   (N 64, K 288)
+constexpr int P3F_OFF = P2F_OFF + P2F_N, P3F_N = 8 * 18 * 512;  // conv3 fwd   (N 128, K 576)
+constexpr int P2D_OFF = P3F_OFF + P3F_N, P2D_N = 2 * 18 * 512;  // conv2 dgrad (N 32, K 576)
+constexpr int P3D_OFF = P2D_OFF + P2D_N, P3D_N = 4 * 36 * 512;  // conv3 dgrad (N 64, K 1152)
+constexpr int PFC_OFF = P3D_OFF + P3D_N, PFC_N = 16 * 128 * 10; // fc1 [window][co][n] (backward)
+constexpr int PFF_OFF = PFC_OFF + PFC_N, PFF_N = 64 * 64 * 8;    // fc1 fwd B fragments, k = w*128 + co
+constexpr int PACK_TOTAL = PFF_OFF + PFF_N;
+
+// window-ordered GEMM row r = 4*window + i of a pooled (2x2/s2) 8x8 map -> spatial y*pw + x
+__device__ __forceinline__ int win_pos(int r, int pw) {
+  const int w = r >> 2, i = r & 3;
+  return (2 * (w >> 2) + (i >> 1)) * pw + 2 * (w & 3) + (i & 1);
+}
+
+// Async global -> LDS copy of 16 B per lane (global_load_lds_dwordx4): the LDS destination is the
+// wave-uniform base + lane * 16, so the image it fills is lane-linear (no padding inside a wave's 1 KiB).
+// Issued from inline asm.  With __builtin_amdgcn_global_load_lds the compiler sees an LDS write on the VM counter
+// and drains it (s_waitcnt vmcnt(0)) before the next LDS read, however unrelated - the prefetch then never
+// overlaps the compute it was issued ahead of (seen in the ISA of conv1_wgrad / conv3_fwd).  Here the copy
+// is invisible to the compiler: the consumer must `s_waitcnt vmcnt(0)` itself before the barrier that
+// publishes the buffer (c_dma_wait).  M0 is set inside the asm; no kernel using this sets M0 otherwise
+// (the ISA of these kernels has no other M0 writer: checked when this was introduced).
+__device__ __forceinline__ void glds16_async(const void* gsrc, void* lds_wave_base) {
+  const unsigned base = __builtin_amdgcn_readfirstlane(
+      (unsigned)(size_t)((__attribute__((address_space(3))) char*)(lds_wave_base)));
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(base), "v"(gsrc) : "memory");
+}
+__device__ __forceinline__ void c_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// the same with the wave's N newest vector-memory operations (stores issued after its DMAs) left in flight
+template <int N>
+__device__ __forceinline__ void c_dma_wait_but() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+// The same copy from a wave-uniform base (SGPR pair) plus a 32-bit per-lane byte offset: the per-lane part of
+// an image's copy is the same for every image, so it is computed once and no 64-bit address math runs per copy.
+__device__ __forceinline__ void glds16_sv(const void* sbase, uint32_t voff, void* lds_wave_base) {
+  const unsigned base = __builtin_amdgcn_readfirstlane(
+      (unsigned)(size_t)((__attribute__((address_space(3))) char*)(lds_wave_base)));
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(base), "v"(voff), "s"(sbase)
+               : "memory");
+}
+
+// barrier for LDS hand-offs: this wave's LDS operations drained, global stores left in flight (the release
+// fence of __syncthreads() would also wait for those)
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+constexpr int C3_XRS = 72;  // bf16 per padded LDS row of a2 (backward wgrad role)
+
+// a2 image -> LDS staging buffer R (lane-linear 16-B chunks, LDS-DMA: no VGPRs, lands while the
+// previous image computes); nthreads threads issue the 13 wave-instructions (the last half full).
+__device__ __forceinline__ void a2_glds(const bf16* __restrict__ a2, int b, bf16* R, int wave, int lane,
+                                        int nwaves) {
+  const bf16* src = a2 + (int64_t)b * 6400;
+  for (int k = wave; k < 13; k += nwaves) {
+    const int slot = k * 64 + lane;
+    if (slot < 800) glds16_async(src + slot * 8, R + k * 512);
+  }
+}
+
+// staging buffer -> padded MFMA rows (RS elements per row, C3_XRS by default): the padding keeps the 16
+// rows of a fragment read on distinct banks, which a lane-linear DMA image cannot have
+template <int RS = C3_XRS>
+__device__ __forceinline__ void a2_relayout(const bf16* R, bf16* X, int tid, int nthreads) {
+  for (int c = tid; c < 800; c += nthreads)
+    *reinterpret_cast<bf16x8*>(X + (c >> 3) * RS + (c & 7) * 8) = reinterpret_cast<const bf16x8*>(R)[c];
+}
+
+// Phase stamps of the diagnostic builds (FF_ST / C3_ST / C12_ST, each enabled by its own -DRINGDP_*_STAMPS and
+// empty otherwise): lane 0 of every wave records s_memtime at phase point k of step s, for the 8 steps from s0,
+// as [wave][step][slots] 8-byte words in the kernel's LDS array `smem` past its lds_end bytes.
+#define CN_STAMP(lds_end, s0, slots, s, k)                                                                         \
+  do {                                                                                                             \
+    if ((s) >= (s0) && (s) < (s0) + 8 && (threadIdx.x & 63) == 0)                                                  \
+      reinterpret_cast<unsigned long long*>(smem + (lds_end))[((threadIdx.x >> 6) * 8 + ((s) - (s0))) * (slots) + (k)] = \
+          __builtin_amdgcn_s_memtime();                                                                            \
+  } while (0)
+
+}  // namespace
+}  // namespace ringdp::kern

@@ -1,6 +1,7 @@
-"""CPU checks of the constant tables baked into csrc/kernels/convnet.hip: the m-tile -> position maps
-of the conv2 forward / dgrad kernels must be permutations of the output positions (padding = 255), and
+"""CPU checks of the constant tables baked into the bf16 ConvNet kernels (csrc/kernels/convnet*): the m-tile ->
+position maps of the conv2 forward / dgrad kernels must be permutations of the output positions (padding = 255), and
 the LDS bank model they were generated with must report the conflict-free schedule they promise."""
+import glob
 import os
 import re
 
@@ -10,9 +11,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def table(name):
-    src = open(os.path.join(ROOT, "csrc", "kernels", "convnet.hip")).read()
-    m = re.search(r"__constant__ uint8_t %s\[(\d+)\] = \{([^}]*)\};" % name, src)
-    assert m, name
+    files = sorted(glob.glob(os.path.join(ROOT, "csrc", "kernels", "convnet*")))
+    found = [m for f in files
+             for m in re.finditer(r"__constant__ uint8_t %s\[(\d+)\] = \{([^}]*)\};" % name, open(f).read())]
+    assert len(found) == 1, (name, len(found))  # defined exactly once in the tree
+    m = found[0]
     vals = [int(v) for v in m.group(2).split(",")]
     assert len(vals) == int(m.group(1))
     return vals

@@ -2,11 +2,13 @@
 with the current in-tree objects into variants/<name>.so (run with RINGDP_EXT_PATH=variants/<name>.so,
 tools/gpu_ab_variants.sh).  usage: python tools/build_variant.py NAME csrc/kernels/x.hip -DFOO=1 ...
 
-This is the only way to the diagnostic-build macros of csrc/kernels/convnet.hip: the timing-only phase
+This is the only way to the diagnostic-build macros of the bf16 ConvNet kernels.  Each is read by one unit,
+the source to give: FF and C12 in csrc/kernels/convnet.hip, C3 in csrc/kernels/convnet_bwd3.hip
+(the stamp macro they share, convnet_device.h, expands in that unit).  They are the timing-only phase
 ablations (wrong results) -DRINGDP_FF_ABLATE=n / -DRINGDP_C3_ABLATE=n / -DRINGDP_C12_ABLATE=n (bits at each
 macro), the fused forward's phase stamps -DRINGDP_FF_STAMPS, those of the 8-wave conv3 dgrad role
 -DRINGDP_C3_STAMPS and those of both roles of the 8-wave conv12 backward -DRINGDP_C12_STAMPS, e.g.
-  python tools/build_variant.py c3_nowgrad csrc/kernels/convnet.hip -DRINGDP_C3_ABLATE=4"""
+  python tools/build_variant.py c3_nowgrad csrc/kernels/convnet_bwd3.hip -DRINGDP_C3_ABLATE=4"""
 import importlib.util
 import sys
 from pathlib import Path
