@@ -1,4 +1,4 @@
-// bf16 ConvNet (design: convnet.hip), F3 backward: fc1 backward, the 4-wave and the 8-wave conv3 backward
+// bf16 ConvNet (design: convnet_fwd.hip), F3 backward: fc1 backward, the 4-wave and the 8-wave conv3 backward
 // (data gradient through pool2 + ReLU, weight gradient), their work split and launcher.
 #include "convnet_device.h"
 #include "convnet_host.h"

@@ -1,5 +1,6 @@
-// bf16 ConvNet (design: convnet.hip): what both convnet.hip and convnet_bwd3.hip use on the device - the packed-weight
-// layout, the LDS-DMA copies, the a2 staging and the phase-stamp macro.
+// bf16 ConvNet (design: convnet_fwd.hip): what more than one of its units (convnet_fwd.hip, convnet_bwd12.hip,
+// convnet_bwd3.hip) uses on the device - the packed-weight layout, the LDS-DMA copies, the a2 and conv1 input
+// staging, the a1 / pool1-code image sizes and the phase-stamp macro.
 #pragma once
 
 #include "device_common.h"
@@ -76,6 +77,77 @@ __device__ __forceinline__ void a2_relayout(const bf16* R, bf16* X, int tid, int
   for (int c = tid; c < 800; c += nthreads)
     *reinterpret_cast<bf16x8*>(X + (c >> 3) * RS + (c & 7) * 8) = reinterpret_cast<const bf16x8*>(R)[c];
 }
+
+// ------------------------------------------------------------------ conv1 input staging (forward and conv1 wgrad)
+// The zero-ringed 30x30 input is staged as 8 copies shifted by s = 0..7 columns (rows of 32):
+// copy s holds xpad[r][c + s].  Eight consecutive pixels xpad[r][ow .. ow+7] are then ONE aligned
+// ds_read_b128 at copy (ow & 7), column (ow & ~7) - this is the im2col of a 5-wide filter row, so
+// the GEMM K is laid out as k = kh*8 + kw (kw < 5 valid): 2 k-steps of 32, no per-element gather.
+constexpr int XC_W = 32, XC_SZ = 30 * XC_W;  // one shifted copy (bf16)
+
+template <bool U8>
+__device__ __forceinline__ void c1_load(const void* xin, int b, int tid, uint32_t& u, float4& f) {
+  if (tid < 196) {
+    if (U8)
+      u = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(xin) + (int64_t)b * 784)[tid];
+    else
+      f = reinterpret_cast<const float4*>(static_cast<const float*>(xin) + (int64_t)b * 784)[tid];
+  }
+}
+
+// Normalise this thread's 4 pixels (one row segment: columns pc0 .. pc0+3, pc0 = 4*(tid%7) + 1) and
+// write them into copies 0..NC-1.  pc0 = 1 (mod 4), so each copy's alignment is known at compile time:
+// one ds_write_b64 (s = 1 mod 4), two b32 (s = 3 mod 4) or b16 + b32 + b16 - instead of 4 b16 per copy.
+// A segment starting at pc0 = 1 writes columns 1-s .. < 0 of copy s "before" its row, i.e. into columns
+// 33-s+k of the previous row: those are only ever read as filter columns kw >= 5 (zero weights in the
+// forward, zero dC rows >= 26 in wgrad), so the spill is harmless and the zero ring (copy column 29-s,
+// column 0 of copy 0, rows 0/29) is never written.
+template <bool U8, int NC, int RS = XC_W, int CS = XC_SZ>
+__device__ __forceinline__ void c1_store(bf16* xc, int tid, uint32_t u, float4 f, float mean, float inv_std,
+                                         float in_scale) {
+  if (tid < 196) {
+    float v[4];
+    if (U8) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = (float)((u >> (8 * k)) & 0xff) * in_scale;
+    } else {
+      v[0] = f.x;
+      v[1] = f.y;
+      v[2] = f.z;
+      v[3] = f.w;
+    }
+    bf16 xv[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) xv[k] = (bf16)((v[k] - mean) * inv_std);
+    const uint32_t lo16 = __builtin_bit_cast(uint16_t, xv[0]), m1 = __builtin_bit_cast(uint16_t, xv[1]),
+                   m2 = __builtin_bit_cast(uint16_t, xv[2]), hi16 = __builtin_bit_cast(uint16_t, xv[3]);
+    const uint32_t p01 = lo16 | (m1 << 16), p23 = m2 | (hi16 << 16), p12 = m1 | (m2 << 16);
+    const int pr = tid / 7 + 1, pc0 = 4 * (tid % 7) + 1;
+#pragma unroll
+    for (int s = 0; s < NC; ++s) {
+      bf16* d = xc + s * CS + pr * RS + pc0 - s;  // may point before the row (see above)
+      if ((s & 3) == 1) {
+        *reinterpret_cast<uint2*>(d) = make_uint2(p01, p23);
+      } else if ((s & 3) == 3) {
+        reinterpret_cast<uint32_t*>(d)[0] = p01;
+        reinterpret_cast<uint32_t*>(d)[1] = p23;
+      } else {
+        d[0] = xv[0];
+        *reinterpret_cast<uint32_t*>(d + 1) = p12;
+        d[3] = xv[3];
+      }
+    }
+  }
+}
+
+// conv1 pool/ReLU codes for the backward: [B][py 13][co/2 16][px 16] bytes (px 13..15 zero), one nibble per
+// channel (low: even co, high: odd co), each 1 << argmax (dy*2+dx) if the pooled value is > 0, else 0 (the
+// gradient's destination, one-hot).  Window rows per channel pair let conv1 wgrad read the codes of 4
+// neighbouring windows of one channel as one 4-byte load.  (Nibbles, not bytes: conv1 forward is bound by
+// its HBM writes, 17.4 -> 14.1 KB per image.)
+constexpr int C1I_IMG = 13 * 256;      // 3328 bytes per image
+constexpr int C1A_IMG = 169 * 32;      // a1 elements per image
+constexpr int C2_XRS = 48;  // bf16 per LDS row of the a1 image (32 + 16 pad): 96-B rows, see c2f_tile_pos
 
 // Phase stamps of the diagnostic builds (FF_ST / C3_ST / C12_ST, each enabled by its own -DRINGDP_*_STAMPS and
 // empty otherwise): lane 0 of every wave records s_memtime at phase point k of step s, for the 8 steps from s0,

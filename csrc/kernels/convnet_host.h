@@ -1,4 +1,4 @@
-// Host helpers shared by the bf16 ConvNet units (convnet.hip, convnet_bwd3.hip); defined in convnet.hip unless inline.
+// Host helpers shared by the bf16 ConvNet units; defined in convnet_reduce.hip unless inline.
 #pragma once
 
 #include <algorithm>

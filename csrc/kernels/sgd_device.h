@@ -1,4 +1,4 @@
-// SGD element math shared by the optimizer kernels (elementwise.hip: flat / multi-tensor; convnet.hip: the
+// SGD element math shared by the optimizer kernels (elementwise.hip: flat / multi-tensor; convnet_fwd.hip: the
 // flat step that also writes the ConvNet's packed bf16 weights).  Parity: torch/optim/sgd.py:343-380.
 #pragma once
 

@@ -364,7 +364,7 @@ std::tuple<at::Tensor, at::Tensor> cn_conv1_fwd(const at::Tensor& x, const at::T
   check_f32_out(b1, {32}, "conv1 bias");
   auto opt = x.options();
   at::Tensor a1 = at::empty({B, 13, 13, 32}, opt.dtype(at::kBFloat16));
-  // pool1 codes in window rows per channel pair [B][py][co/2][px (13 + 3 zero)][co&1] (see convnet.hip F1)
+  // pool1 codes in window rows per channel pair [B][py][co/2][px (13 + 3 zero)][co&1] (see convnet_device.h, C1I_IMG)
   at::Tensor idx = at::empty({B, 13, 16, 16}, opt.dtype(at::kByte));
   if (B == 0) return {a1, idx};
   kern::cn_conv1_fwd(x.data_ptr(), u8, packed.data_ptr(), b1.data_ptr<float>(), a1.data_ptr(),

@@ -1,4 +1,4 @@
-"""Autograd Functions for the MNIST ConvNet hot path (csrc/kernels/convnet.hip, convnet_bwd3.hip).
+"""Autograd Functions for the MNIST ConvNet hot path (csrc/kernels/convnet_*.hip).
 
 The whole forward (reference layers ref/launch_dist.py:35-41) is ONE launch, ``C.cn_forward_fused``: conv1 +
 ReLU + pool1 (+ fused ToTensor/Normalize for uint8 input), conv2 + ReLU + overlapping pool2, conv3 + ReLU +

@@ -1,7 +1,7 @@
 """Numerics of ringdp's ConvNet HIP kernels against plain PyTorch fp32 references (same ops,
 inputs rounded to bf16 the way the kernels consume them).
 
-Blocks under test (csrc/kernels/convnet.hip): F1 conv1+relu+pool1, F2 conv2+relu+pool2 (with pool2
+Blocks under test (csrc/kernels/convnet_*.hip): F1 conv1+relu+pool1, F2 conv2+relu+pool2 (with pool2
 codes), F3 conv3+relu+pool3+fc1, their backward kernels and the weight packer."""
 import pytest
 import torch

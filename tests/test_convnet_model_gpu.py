@@ -230,7 +230,7 @@ def _bf16_oracle_forward(m, x):
     x = (x.float() / 255.0 - 0.1307) / 0.3081
     w1, w2, w3, wf = (_rb(p) for p in (m.conv1.weight, m.conv2.weight, m.conv3.weight, m.fc1.weight))
     a = _rb(F.max_pool2d(F.relu(F.conv2d(_rb(x), w1, m.conv1.bias, padding=1)), 2, 2))
-    # conv2's pre-activation is staged as bf16 before the overlapping pool (csrc/kernels/convnet.hip F2), so
+    # conv2's pre-activation is staged as bf16 before the overlapping pool (csrc/kernels/convnet_fwd.hip F2), so
     # its argmax ties are broken on bf16 values: round before the pool too
     a = _rb(F.max_pool2d(F.relu(_rb(F.conv2d(a, w2, m.conv2.bias))), 2, 1))
     a = _rb(F.max_pool2d(F.relu(F.conv2d(a, w3, m.conv3.bias)), 2, 2))

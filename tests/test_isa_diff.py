@@ -87,3 +87,30 @@ def test_missing_kernel(tmp_path):
 def test_kernel_defined_twice(tmp_path):
     r = run(tmp_path, [asm(["k_one"])], [asm(["k_one"]), asm(["k_one"], n0=1)])
     assert r.returncode != 0
+
+
+def diff_fields(stdout, name):
+    """(lines only in A, lines only in B, class) of kernel `name`'s DIFF line."""
+    (line,) = [l.split() for l in stdout.splitlines() if l.split()[0] == "DIFF" and l.split()[-1] == name]
+    return line[3], line[4], line[5]
+
+
+def test_diff_counts_lines_and_says_code(tmp_path):
+    # one instruction replaced: one line on each side; one replaced by two: the listing is one line longer
+    r = run(tmp_path, [asm(["k_one", "k_two"])],
+            [asm(["k_one"], insn="v_add_u32_e32 v1, v0, v1"),
+             asm(["k_two"], n0=1, insn="v_add_u32_e32 v1, v0, v1\n\ts_nop 0")])
+    assert r.returncode != 0
+    assert diff_fields(r.stdout, "k_one") == ("-1", "+1", "code")
+    assert diff_fields(r.stdout, "k_two") == ("-1", "+2", "code")
+    assert "- v_add_u32_e32 v1, v0, v0" in r.stdout and "+ s_nop 0" in r.stdout  # the differing lines are listed
+
+
+def test_diff_says_descriptor(tmp_path):
+    # a changed register budget is a descriptor difference, with or without a code difference beside it
+    r = run(tmp_path, [asm(["k_one", "k_two"])],
+            [asm(["k_one"], vgpr=3), asm(["k_two"], n0=1, vgpr=3, insn="v_add_u32_e32 v1, v0, v1")])
+    assert r.returncode != 0
+    assert diff_fields(r.stdout, "k_one") == ("-1", "+1", "descriptor")
+    assert diff_fields(r.stdout, "k_two") == ("-2", "+2", "descriptor")
+    assert "same" not in r.stdout

@@ -3,7 +3,7 @@ with the current in-tree objects into variants/<name>.so (run with RINGDP_EXT_PA
 tools/gpu_ab_variants.sh).  usage: python tools/build_variant.py NAME csrc/kernels/x.hip -DFOO=1 ...
 
 This is the only way to the diagnostic-build macros of the bf16 ConvNet kernels.  Each is read by one unit,
-the source to give: FF and C12 in csrc/kernels/convnet.hip, C3 in csrc/kernels/convnet_bwd3.hip
+the source to give: FF in csrc/kernels/convnet_fwd.hip, C12 in convnet_bwd12.hip, C3 in convnet_bwd3.hip
 (the stamp macro they share, convnet_device.h, expands in that unit).  They are the timing-only phase
 ablations (wrong results) -DRINGDP_FF_ABLATE=n / -DRINGDP_C3_ABLATE=n / -DRINGDP_C12_ABLATE=n (bits at each
 macro), the fused forward's phase stamps -DRINGDP_FF_STAMPS, those of the 8-wave conv3 dgrad role

@@ -5,11 +5,15 @@ cut at its `; -- Begin function NAME` / `; -- End function` markers (the kernel 
 register and LDS budget, lies inside them); `;` comments and blank lines are dropped, the numbering of local labels
 (.LBB<n>_, .Ltmp<n>, .Lfunc_begin<n>, .Lfunc_end<n>) and the per-file __hip_cuid_* symbol are normalised.  The
 kernels of each side are the union over its files.  One line per kernel, `same` or `DIFF`, with the instruction-line
-counts; exit status 1 on any difference, on a kernel one side lacks, or on a kernel one side defines twice.  A plain
-diff: it looks for no particular instruction.
+counts; a `DIFF` line also says how many normalised lines differ (-only in A, +only in B) and whether an .amdhsa_
+line is among them (`descriptor`: the register or LDS budget changed) or not (`code`), and the differing lines
+follow it.  Exit status 1 on any difference, on a kernel one side lacks, or on a kernel one side defines twice.
+A plain diff: it looks for no particular instruction.
 
-Used to show that moving kernels between translation units left their code unchanged, e.g. the parent's
-convnet.hip against the new convnet.hip and convnet_bwd3.hip (profiles/r08/convnet_split)."""
+Used to show what moving kernels between translation units did to their code, e.g. the one bf16 ConvNet file
+against its units convnet_fwd.hip, convnet_bwd12.hip, convnet_bwd3.hip and convnet_reduce.hip
+(profiles/r08/convnet_split, profiles/r09/convnet_units)."""
+import difflib
 import re
 import sys
 
@@ -63,9 +67,19 @@ def main(argv):
             print(f"ONLY {'A' if n in a else 'B'}  {n}")
             bad += 1
             continue
-        same = a[n] == b[n]
-        bad += not same
-        print(f"{'same' if same else 'DIFF'}  {len(a[n]):6d} {len(b[n]):6d}  {n}")
+        if a[n] == b[n]:
+            print(f"same  {len(a[n]):6d} {len(b[n]):6d}  {n}")
+            continue
+        bad += 1
+        delta = []  # the lines only one side has, in order
+        for tag, i1, i2, j1, j2 in difflib.SequenceMatcher(None, a[n], b[n], autojunk=False).get_opcodes():
+            if tag != "equal":
+                delta += [("-", l) for l in a[n][i1:i2]] + [("+", l) for l in b[n][j1:j2]]
+        minus = sum(sign == "-" for sign, _ in delta)
+        kind = "descriptor" if any(l.startswith(".amdhsa_") for _, l in delta) else "code"
+        print(f"DIFF  {len(a[n]):6d} {len(b[n]):6d}  -{minus} +{len(delta) - minus} {kind}  {n}")
+        for sign, l in delta:
+            print(f"      {sign} {l}")
     if not a and not b:
         print("no function markers found")
         bad += 1
