@@ -516,6 +516,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sgd_multi_run", &ops::sgd_multi_run, py::arg("table"), py::arg("nchunks"),
         py::arg("table_bytes"), py::arg("hyper"), py::arg("first_step"),
         py::arg("lr_tensor") = py::none(), py::arg("grad_scale") = py::none());
+  py::class_<ops::AdamHyper>(m, "AdamHyper")
+      .def(py::init<>())
+      .def_readwrite("lr", &ops::AdamHyper::lr)
+      .def_readwrite("beta1", &ops::AdamHyper::beta1)
+      .def_readwrite("beta2", &ops::AdamHyper::beta2)
+      .def_readwrite("eps", &ops::AdamHyper::eps)
+      .def_readwrite("weight_decay", &ops::AdamHyper::weight_decay)
+      .def_readwrite("maximize", &ops::AdamHyper::maximize)
+      .def_readwrite("decoupled", &ops::AdamHyper::decoupled);
+  py::class_<ops::AdamTable>(m, "AdamTable")
+      .def_property_readonly("nchunks", &ops::AdamTable::nchunks)
+      .def_readonly("chunk_starts", &ops::AdamTable::chunk_starts)
+      .def_readonly("all_aligned", &ops::AdamTable::all_aligned)
+      .def_readonly("full", &ops::AdamTable::full);
+  m.def("adam_table_build", &ops::adam_table_build, py::arg("params"), py::arg("grads"), py::arg("exp_avgs"),
+        py::arg("exp_avg_sqs"), py::arg("group_sizes"));
+  m.def("grad_sumsq_run", &ops::grad_sumsq_run, py::arg("table"), py::arg("partials"));
+  m.def("adam_prepare_run", &ops::adam_prepare_run, py::arg("rec"), py::arg("partials"), py::arg("npartials"),
+        py::arg("max_norm"), py::arg("steps"), py::arg("lr_tensors"), py::arg("hypers"));
+  m.def("adam_update_run", &ops::adam_update_run, py::arg("table"), py::arg("table_group"), py::arg("rec"),
+        py::arg("rec_group"), py::arg("hyper"));
+  m.def("adam_update_flat", &ops::adam_update_flat, py::arg("param"), py::arg("grad"), py::arg("exp_avg"),
+        py::arg("exp_avg_sq"), py::arg("rec"), py::arg("rec_group"), py::arg("hyper"));
+  m.def("grad_scale_run", &ops::grad_scale_run, py::arg("table"), py::arg("rec"));
   m.def("cross_entropy_fwd", &ops::cross_entropy_fwd);
   m.def("cross_entropy_bwd", &ops::cross_entropy_bwd);
   // roctx tracing (rocprofv3 --marker-trace)

@@ -43,6 +43,55 @@ struct SgdTensor {
 void sgd_multi(const SgdTensor* table, const int64_t* chunks, int64_t nchunks, int64_t chunk_elems,
                const SgdArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------- Adam / AdamW + global-norm clipping (optim.hip)
+// No atomics, arrival counters or fences: grad_sumsq -> adam_prepare -> adam_update are ordered by kernel
+// boundaries on one stream, so a step is deterministic and hipGraph-capturable.
+struct AdamTensor {  // p / m / v may be null in a table that only the gradient kernels walk
+  float* p;
+  float* g;
+  float* m;
+  float* v;
+  int64_t n;
+};
+constexpr int64_t kAdamChunk = 65536;  // elements one workgroup covers in the table kernels
+constexpr int kAdamMaxGroups = 32;
+// Device record, floats: [0..3] = {total_norm, clip_coef, 0, 0}, then per group g at [4 + 4g ..] =
+// {lr, step_size = lr / bc1, 1 / sqrt(bc2), clip_coef}.
+constexpr int kAdamRecHead = 4;
+constexpr int kAdamRecGroup = 4;
+struct AdamGroupPrep {
+  float* step;          // device step counter (fp32, as torch keeps it); incremented by adam_prepare
+  const float* lr_ptr;  // optional device-resident lr (overrides `lr`)
+  float lr;
+  double beta1, beta2;
+};
+struct AdamPrepArgs {
+  const float* partials;  // one sum of squares per chunk (grad_sumsq); null: no clipping
+  int64_t npartials;
+  float max_norm;
+  float* rec;
+  int ngroups;
+  AdamGroupPrep group[kAdamMaxGroups];
+};
+struct AdamArgs {
+  double weight_decay;
+  float beta2, one_minus_beta1, one_minus_beta2, eps;
+  bool maximize;
+  const float* rec;  // this group's 16-byte-aligned record
+};
+// partials[c] = sum of g^2 over chunk c = {tensor, start} (fixed mapping and reduction tree).
+void grad_sumsq(const AdamTensor* table, const int64_t* chunks, int64_t nchunks, float* partials, hipStream_t s);
+void adam_prepare(const AdamPrepArgs& a, hipStream_t s);
+// all_aligned: every p / g / m / v base of the walked chunks is 16-byte aligned (else checked per chunk).
+void adam_update_multi(const AdamTensor* table, const int64_t* chunks, int64_t nchunks, const AdamArgs& a,
+                       bool decoupled, bool all_aligned, hipStream_t s);
+// Flat range, all four buffers 16-byte aligned.
+void adam_update_flat(float* p, const float* g, float* m, float* v, int64_t n, const AdamArgs& a, bool decoupled,
+                      hipStream_t s);
+// g *= clip_coef (rec[1]) in place over the table.
+void grad_scale_multi(const AdamTensor* table, const int64_t* chunks, int64_t nchunks, const float* rec,
+                      hipStream_t s);
+
 // Deterministic split-K reduction: out[i] = sum_s slabs[s * n + i] (fixed order).
 void splitk_reduce(const float* slabs, int nslices, int64_t n, float* out, hipStream_t s);
 

@@ -257,6 +257,205 @@ void sgd_multi(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
   sgd_multi_run(std::get<0>(t), std::get<1>(t), std::get<2>(t), h, first_step, lr_t, scale_t);
 }
 
+// ------------------------------------------------------------------ Adam / AdamW
+namespace {
+
+const kern::AdamTensor* adam_entries(const AdamTable& t) {
+  RINGDP_CHECK(t.dev.defined() && t.table_bytes > 0, "adam table: not built");
+  return reinterpret_cast<const kern::AdamTensor*>(t.dev.data_ptr());
+}
+
+const int64_t* adam_chunks(const AdamTable& t) {
+  return reinterpret_cast<const int64_t*>(static_cast<char*>(t.dev.data_ptr()) + t.table_bytes);
+}
+
+const float* adam_rec(const at::Tensor& rec, int64_t groups) {
+  check_cuda(rec, "adam record");
+  check_dtype(rec, at::kFloat, "adam record");
+  RINGDP_CHECK(rec.numel() >= kern::kAdamRecHead + kern::kAdamRecGroup * groups, "adam record: ", rec.numel(),
+               " floats cannot hold ", groups, " group(s)");
+  RINGDP_CHECK(aligned16(rec), "adam record: must be 16-byte aligned");
+  return rec.data_ptr<float>();
+}
+
+kern::AdamArgs adam_args(const AdamHyper& h, const at::Tensor& rec, int64_t group) {
+  RINGDP_CHECK(group >= 0, "adam: negative group index");
+  kern::AdamArgs a{};
+  a.beta2 = static_cast<float>(h.beta2);
+  a.one_minus_beta1 = static_cast<float>(1.0 - h.beta1);
+  a.one_minus_beta2 = static_cast<float>(1.0 - h.beta2);
+  a.eps = static_cast<float>(h.eps);
+  a.weight_decay = h.weight_decay;
+  a.maximize = h.maximize;
+  a.rec = adam_rec(rec, group + 1) + kern::kAdamRecHead + kern::kAdamRecGroup * group;
+  return a;
+}
+
+}  // namespace
+
+AdamTable adam_table_build(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
+                           std::vector<at::Tensor> exp_avgs, std::vector<at::Tensor> exp_avg_sqs,
+                           std::vector<int64_t> group_sizes) {
+  const size_t n = grads.size();
+  const bool full = !params.empty();
+  RINGDP_CHECK(n > 0, "adam_table_build: no tensors");
+  if (full)
+    RINGDP_CHECK(params.size() == n && exp_avgs.size() == n && exp_avg_sqs.size() == n,
+                 "adam_table_build: need one grad, exp_avg and exp_avg_sq per param");
+  else
+    RINGDP_CHECK(exp_avgs.empty() && exp_avg_sqs.empty(), "adam_table_build: state tensors without params");
+  int64_t covered = 0;
+  for (int64_t gs : group_sizes) {
+    RINGDP_CHECK(gs >= 0, "adam_table_build: negative group size");
+    covered += gs;
+  }
+  RINGDP_CHECK(covered == static_cast<int64_t>(n), "adam_table_build: group sizes cover ", covered, " of ", n,
+               " tensors");
+  std::vector<kern::AdamTensor> table(n);
+  std::vector<int64_t> chunks, starts{0};
+  std::vector<bool> aligned;
+  size_t i = 0;
+  for (int64_t gs : group_sizes) {
+    bool al = true;
+    for (const size_t end = i + static_cast<size_t>(gs); i < end; ++i) {
+      check_cuda(grads[i], "adam grad");
+      check_dtype(grads[i], at::kFloat, "adam grad");
+      RINGDP_CHECK(grads[i].get_device() == grads[0].get_device(), "adam_table_build: tensors on several devices");
+      kern::AdamTensor e{nullptr, grads[i].data_ptr<float>(), nullptr, nullptr, grads[i].numel()};
+      al = al && aligned16(grads[i]);
+      if (full) {
+        const at::Tensor* ts[3] = {&params[i], &exp_avgs[i], &exp_avg_sqs[i]};
+        const char* names[3] = {"adam param", "adam exp_avg", "adam exp_avg_sq"};
+        for (int k = 0; k < 3; ++k) {
+          check_cuda(*ts[k], names[k]);
+          check_dtype(*ts[k], at::kFloat, names[k]);
+          RINGDP_CHECK(ts[k]->numel() == e.n, names[k], ": numel mismatch with the grad at ", i);
+          RINGDP_CHECK(ts[k]->get_device() == grads[0].get_device(), "adam_table_build: tensors on several devices");
+          al = al && aligned16(*ts[k]);
+        }
+        e.p = params[i].data_ptr<float>();
+        e.m = exp_avgs[i].data_ptr<float>();
+        e.v = exp_avg_sqs[i].data_ptr<float>();
+      }
+      table[i] = e;
+      for (int64_t s = 0; s < e.n; s += kern::kAdamChunk) {
+        chunks.push_back(static_cast<int64_t>(i));
+        chunks.push_back(s);
+      }
+    }
+    starts.push_back(static_cast<int64_t>(chunks.size() / 2));
+    aligned.push_back(al);
+  }
+  const int64_t tbytes = static_cast<int64_t>(table.size() * sizeof(kern::AdamTensor));
+  const int64_t cbytes = static_cast<int64_t>(chunks.size() * sizeof(int64_t));
+  at::Tensor host = at::empty({tbytes + cbytes}, at::TensorOptions().dtype(at::kByte));
+  std::memcpy(host.data_ptr(), table.data(), tbytes);
+  if (cbytes > 0) std::memcpy(static_cast<char*>(host.data_ptr()) + tbytes, chunks.data(), cbytes);
+  AdamTable t;
+  t.dev = host.to(grads[0].device());  // synchronous: safe to cache and reuse
+  t.table_bytes = tbytes;
+  t.chunk_starts = starts;
+  t.all_aligned = aligned;
+  t.full = full;
+  return t;
+}
+
+void grad_sumsq_run(const AdamTable& table, at::Tensor partials) {
+  const kern::AdamTensor* entries = adam_entries(table);
+  check_cuda(partials, "grad_sumsq partials");
+  check_dtype(partials, at::kFloat, "grad_sumsq partials");
+  RINGDP_CHECK(partials.numel() >= table.nchunks(), "grad_sumsq: ", partials.numel(), " partials for ",
+               table.nchunks(), " chunks");
+  RINGDP_CHECK(partials.get_device() == table.dev.get_device(), "grad_sumsq: partials on another device");
+  c10::DeviceGuard guard(table.dev.device());
+  kern::grad_sumsq(entries, adam_chunks(table), table.nchunks(), partials.data_ptr<float>(), cur_stream(table.dev));
+}
+
+void adam_prepare_run(at::Tensor rec, const c10::optional<at::Tensor>& partials, int64_t npartials, double max_norm,
+                      std::vector<at::Tensor> steps, std::vector<c10::optional<at::Tensor>> lr_tensors,
+                      const std::vector<AdamHyper>& hypers) {
+  const size_t G = steps.size();
+  RINGDP_CHECK(G <= static_cast<size_t>(kern::kAdamMaxGroups), "adam_prepare: at most ", kern::kAdamMaxGroups,
+               " parameter groups per launch, got ", G);
+  RINGDP_CHECK(lr_tensors.size() == G && hypers.size() == G, "adam_prepare: one lr and hyper set per group");
+  kern::AdamPrepArgs a{};
+  a.rec = const_cast<float*>(adam_rec(rec, static_cast<int64_t>(G)));
+  a.ngroups = static_cast<int>(G);
+  if (partials.has_value() && partials->defined()) {
+    check_cuda(*partials, "adam_prepare partials");
+    check_dtype(*partials, at::kFloat, "adam_prepare partials");
+    RINGDP_CHECK(npartials >= 0 && npartials <= partials->numel(), "adam_prepare: ", npartials, " of ",
+                 partials->numel(), " partials");
+    RINGDP_CHECK(partials->get_device() == rec.get_device(), "adam_prepare: partials on another device");
+    RINGDP_CHECK(max_norm >= 0.0, "adam_prepare: max_norm must be non-negative, got ", max_norm);
+    a.partials = partials->data_ptr<float>();
+    a.npartials = npartials;
+    a.max_norm = static_cast<float>(max_norm);
+  }
+  for (size_t g = 0; g < G; ++g) {
+    check_cuda(steps[g], "adam step counter");
+    check_dtype(steps[g], at::kFloat, "adam step counter");
+    RINGDP_CHECK(steps[g].numel() == 1, "adam step counter: expected one element");
+    RINGDP_CHECK(steps[g].get_device() == rec.get_device(), "adam step counter on another device");
+    kern::AdamGroupPrep& gp = a.group[g];
+    gp.step = steps[g].data_ptr<float>();
+    gp.lr = static_cast<float>(hypers[g].lr);
+    gp.beta1 = hypers[g].beta1;
+    gp.beta2 = hypers[g].beta2;
+    if (lr_tensors[g].has_value() && lr_tensors[g]->defined()) {
+      const at::Tensor& lr = *lr_tensors[g];
+      check_cuda(lr, "lr tensor");
+      check_dtype(lr, at::kFloat, "lr tensor");
+      RINGDP_CHECK(lr.numel() == 1, "lr tensor: expected one element");
+      RINGDP_CHECK(lr.get_device() == rec.get_device(), "lr tensor on another device");
+      gp.lr_ptr = lr.data_ptr<float>();
+    }
+  }
+  c10::DeviceGuard guard(rec.device());
+  kern::adam_prepare(a, cur_stream(rec));
+}
+
+void adam_update_run(const AdamTable& table, int64_t table_group, const at::Tensor& rec, int64_t rec_group,
+                     const AdamHyper& h) {
+  const kern::AdamTensor* entries = adam_entries(table);
+  RINGDP_CHECK(table.full, "adam_update: the table holds gradients only");
+  RINGDP_CHECK(table_group >= 0 && table_group + 1 < static_cast<int64_t>(table.chunk_starts.size()),
+               "adam_update: group ", table_group, " of a table with ", table.chunk_starts.size() - 1, " group(s)");
+  RINGDP_CHECK(rec.get_device() == table.dev.get_device(), "adam_update: record on another device");
+  const int64_t chunk0 = table.chunk_starts[table_group];
+  const int64_t nchunks = table.chunk_starts[table_group + 1] - chunk0;
+  const kern::AdamArgs a = adam_args(h, rec, rec_group);
+  c10::DeviceGuard guard(table.dev.device());
+  kern::adam_update_multi(entries, adam_chunks(table) + 2 * chunk0, nchunks, a, h.decoupled,
+                          table.all_aligned[table_group], cur_stream(table.dev));
+}
+
+void adam_update_flat(at::Tensor param, const at::Tensor& grad, at::Tensor exp_avg, at::Tensor exp_avg_sq,
+                      const at::Tensor& rec, int64_t rec_group, const AdamHyper& h) {
+  const at::Tensor* ts[4] = {&param, &grad, &exp_avg, &exp_avg_sq};
+  const char* names[4] = {"adam param", "adam grad", "adam exp_avg", "adam exp_avg_sq"};
+  for (int k = 0; k < 4; ++k) {
+    check_cuda(*ts[k], names[k]);
+    check_dtype(*ts[k], at::kFloat, names[k]);
+    RINGDP_CHECK(ts[k]->numel() == param.numel(), "adam_update_flat: ", names[k], " numel mismatch");
+    RINGDP_CHECK(ts[k]->get_device() == param.get_device(), "adam_update_flat: ", names[k], " on another device");
+    RINGDP_CHECK(aligned16(*ts[k]), "adam_update_flat: buffers must be 16-byte aligned");
+  }
+  RINGDP_CHECK(rec.get_device() == param.get_device(), "adam_update_flat: record on another device");
+  const kern::AdamArgs a = adam_args(h, rec, rec_group);
+  c10::DeviceGuard guard(param.device());
+  kern::adam_update_flat(param.data_ptr<float>(), grad.data_ptr<float>(), exp_avg.data_ptr<float>(),
+                         exp_avg_sq.data_ptr<float>(), param.numel(), a, h.decoupled, cur_stream(param));
+}
+
+void grad_scale_run(const AdamTable& table, const at::Tensor& rec) {
+  const kern::AdamTensor* entries = adam_entries(table);
+  RINGDP_CHECK(rec.get_device() == table.dev.get_device(), "grad_scale: record on another device");
+  const float* r = adam_rec(rec, 0);
+  c10::DeviceGuard guard(table.dev.device());
+  kern::grad_scale_multi(entries, adam_chunks(table), table.nchunks(), r, cur_stream(table.dev));
+}
+
 // ------------------------------------------------------------------ cross entropy
 std::tuple<at::Tensor, at::Tensor, at::Tensor> cross_entropy_fwd(const at::Tensor& logits,
                                                                  const at::Tensor& labels,

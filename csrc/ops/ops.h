@@ -45,6 +45,47 @@ void sgd_multi_run(const at::Tensor& table, int64_t nchunks, int64_t table_bytes
                    const SgdHyper& h, bool first_step, const c10::optional<at::Tensor>& lr_tensor,
                    const c10::optional<at::Tensor>& grad_scale);
 
+// ---- Adam / AdamW with global-norm clipping (csrc/kernels/optim.hip).  One step is
+// [grad_sumsq_run ->] adam_prepare_run -> adam_update_run / adam_update_flat per group, on one stream.
+struct AdamHyper {
+  double lr = 1e-3;
+  double beta1 = 0.9;
+  double beta2 = 0.999;
+  double eps = 1e-8;
+  double weight_decay = 0.0;
+  bool maximize = false;
+  bool decoupled = true;  // AdamW; false: Adam (decay added to the gradient)
+};
+// Device table over fp32 tensors, listed group after group (group_sizes[i] tensors each): {p, g, m, v, n} entries
+// followed by the {tensor, start} chunk list.  params / exp_avgs / exp_avg_sqs may all be empty (a table for the
+// gradient kernels only).  The upload is synchronous, so the table can be cached and the kernels that walk it
+// captured, same contract as sgd_multi_build.  Everything the launches rely on was checked when it was built.
+struct AdamTable {
+  at::Tensor dev;
+  int64_t table_bytes = 0;
+  std::vector<int64_t> chunk_starts;  // groups + 1 entries
+  std::vector<bool> all_aligned;      // per group: every base 16-byte aligned
+  bool full = false;                  // holds p / m / v, not only gradients
+  int64_t nchunks() const { return chunk_starts.empty() ? 0 : chunk_starts.back(); }
+};
+AdamTable adam_table_build(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
+                           std::vector<at::Tensor> exp_avgs, std::vector<at::Tensor> exp_avg_sqs,
+                           std::vector<int64_t> group_sizes);
+// partials[c] = sum of g^2 over chunk c of the whole table.
+void grad_sumsq_run(const AdamTable& table, at::Tensor partials);
+// One launch per step: total norm and clip coefficient from `partials` (when given), steps[g] += 1, and the
+// per-group records in `rec` (4 + 4 * groups floats; rec[0] = total norm, rec[1] = clip coefficient).
+void adam_prepare_run(at::Tensor rec, const c10::optional<at::Tensor>& partials, int64_t npartials, double max_norm,
+                      std::vector<at::Tensor> steps, std::vector<c10::optional<at::Tensor>> lr_tensors,
+                      const std::vector<AdamHyper>& hypers);
+// Update the tensors of the table's group `table_group` with record `rec_group` of `rec`.
+void adam_update_run(const AdamTable& table, int64_t table_group, const at::Tensor& rec, int64_t rec_group,
+                     const AdamHyper& h);
+void adam_update_flat(at::Tensor param, const at::Tensor& grad, at::Tensor exp_avg, at::Tensor exp_avg_sq,
+                      const at::Tensor& rec, int64_t rec_group, const AdamHyper& h);
+// g *= rec[1] in place over the whole table.
+void grad_scale_run(const AdamTable& table, const at::Tensor& rec);
+
 // Cross entropy: returns (loss, lse, workspace); workspace holds the denominator for backward.
 std::tuple<at::Tensor, at::Tensor, at::Tensor> cross_entropy_fwd(const at::Tensor& logits,
                                                                  const at::Tensor& labels,

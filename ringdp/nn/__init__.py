@@ -1,9 +1,10 @@
-"""ringdp.nn - loss modules backed by ringdp kernels on GPU (ATen on CPU)."""
+"""ringdp.nn - loss modules backed by ringdp kernels on GPU (ATen on CPU); ``ringdp.nn.utils``: gradient clipping."""
 from __future__ import annotations
 
 import torch.nn as _nn
 
 from ..ops.loss import cross_entropy
+from . import utils  # noqa: F401  (ringdp.nn.utils.clip_grad_norm_)
 
 
 class CrossEntropyLoss(_nn.Module):

@@ -1,4 +1,5 @@
 """ringdp.optim - optimizers with fused CDNA4 update kernels."""
+from .adamw import Adam, AdamW  # noqa: F401
 from .sgd import SGD  # noqa: F401
 
-__all__ = ["SGD"]
+__all__ = ["SGD", "Adam", "AdamW"]

@@ -8,7 +8,9 @@ reducer and the collective kernels) into a hipGraph that ``replay()`` launches w
 
 Requirements: inputs the step reads must live in static tensors (copy each new batch into
 them), DDP bucket rebuild must have happened (warmup >= 2 steps), and the optimizer must use
-its graph-safe path (ringdp.optim.SGD flat path: no allocations, lr may be a device tensor).
+its graph-safe path (ringdp.optim.SGD flat path: no allocations, lr may be a device tensor; ringdp.optim.AdamW /
+Adam, flat or multi-tensor once warm-up built their table: the step count, the bias corrections, the clip
+coefficient of max_grad_norm and a tensor lr all live on the device, so every replay advances them).
 """
 from __future__ import annotations
 
