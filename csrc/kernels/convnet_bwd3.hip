@@ -9,7 +9,8 @@ namespace {
 // (1) fc1 backward, one pass over a3: compact data gradient
 //       da3m[b][w][co] = (a3 > 0) * sum_n dl[b][n] * Wfc[n][co*16 + w]     (bf16, Wfc from the pack)
 //     and the fc1 weight/bias gradient of this block's images as an fp32 slab.  The conv3 backward
-//     roles expand da3m to window-ordered rows (row 4w + argmax) in LDS.
+//     roles expand da3m to window-ordered rows (row 4w + argmax) in LDS; the 8-wave weight-gradient role feeds
+//     it, unexpanded, to the sparse MFMA.
 // images per workgroup: enough workgroups to fill the chip at small batches (B=100: 25 of 4 images,
 // was 4 of 32 and latency-bound at 21 us), fewer fp32 slabs at large ones (B=32768: 512 of 64 images,
 // halving the 84 MB of slab traffic)
@@ -507,25 +508,30 @@ __global__ __launch_bounds__(256, 1) void conv3_bwd_kernel(const bf16* __restric
 //     a barrier of all four waves.
 //   wgrad: 8 waves cover the whole 128 x 576 dW3t of their image slice (36 tiles each, 2 x 4 waves), so
 //     an image is staged once (the 4-wave role needs a workgroup pair, each staging every image); image
-//     i+1's operands (compact gradient -> D, a2 -> X by LDS-DMA straight into the padded rows) are staged
-//     while image i's MFMAs run.
+//     i+1's operands (compact gradient -> sparse-MFMA A fragments, a2 -> X by LDS-DMA straight into the padded
+//     rows) are staged while image i's MFMAs run.  The window-ordered d(conv3) rows have one non-zero in every
+//     aligned four (pool3 is 2x2, stride 2), so the product runs on v_smfmac_f32_16x16x64_bf16 straight from
+//     the compact gradient and its argmax bytes: K = 64 in one instruction, half the dense role's MFMAs.
 // All global -> LDS traffic is LDS-DMA from inline asm (invisible to the compiler's vmcnt bookkeeping),
 // waited for explicitly before the barrier; the dz2 stores stay in flight across it.
 // LDS layouts (every fragment read, col2im access and pool2 read modelled conflict-free with the lane
 // groups of MI355X_MICROARCH.md; the 4-wave kernel's layouts measured 30-46 % bank-conflict cycles):
 //   da2 (fp32): 256-B position rows, the 16-B chunk k of position (y, x) at slot k ^ 2(x & 7);
-//   D (wgrad): rows of 144 bf16 in blocks of 8 rows, 1216 bf16 per block (tr16 reads of rows k..k+3 and
-//     k+8..k+11 then cover the 64 banks once);  X (wgrad): a2 rows of 80 bf16 (10 16-B chunks).
+//   F (wgrad): the A operand in fragment order, per m-tile 64 lanes x 16 B of values, then 64 lanes x 4 B of
+//     index words: lane-linear, one ds_read_b128 + one ds_read_b32 per m-tile;  the wgrad role's compact
+//     stage: 16-B chunks XOR-swizzled inside each window by the copy's source offsets (c3w_stage_off), so that
+//     the 2-byte / 1-byte gathers that build F meet no bank twice;  X (wgrad): a2 rows of 80 bf16 (10 16-B
+//     chunks).
 constexpr int C3S_B = 2048 * 2 + 2048;  // compact stage of one image: da3m row (bf16) + pool3 argmax bytes
 constexpr int C3V_DA = 100 * 64 * 4;    // 25600
-constexpr int C3V_D = 8 * 1216 * 2;     // 19456
+constexpr int C3V_FV = 8 * 64 * 16;     // 8192: A values of the 8 m-tiles
+constexpr int C3V_F = C3V_FV + 8 * 64 * 4;  // 10240: + their index words
 constexpr int C3V_XRS = 80;
 constexpr int C3V_X = 100 * C3V_XRS * 2;  // 16000
 constexpr int C3V_DG = 2 * (C3D_P + C3V_DA + C3D_AM + C3S_B);  // 131584
-constexpr int C3V_WG = 3 * (C3V_D + C3V_X) + 2 * C3S_B;        // 118656
+constexpr int C3V_WG = 3 * C3V_X + 2 * C3V_F + 2 * C3S_B;      // 80768
 constexpr int C3V_LDS = C3V_DG > C3V_WG ? C3V_DG : C3V_WG;
-static_assert(C3V_LDS <= 160 * 1024 && C3V_D % 16 == 0 && C3V_X % 16 == 0, "conv3 backward (8-wave) LDS");
-__device__ __forceinline__ int c3v_drow(int r) { return (r >> 3) * 1216 + (r & 7) * 144; }
+static_assert(C3V_LDS <= 160 * 1024 && C3V_F % 16 == 0 && C3V_X % 16 == 0, "conv3 backward (8-wave) LDS");
 // float offset of 16-B chunk k (channels 4k..4k+3) of da2 position p = y * 10 + x
 __device__ __forceinline__ int c3v_da(int p, int x, int k) { return p * 64 + ((k ^ (2 * (x & 7))) << 2); }
 // exact 0.0 / 1.0 of byte J of v (one v_cvt_f32_ubyteJ; the compiler's form of (v >> 8J) & 0xff was a shift,
@@ -561,6 +567,42 @@ __device__ __forceinline__ void c3s_pre(const char* S, int tid, C3Pre& p) {
     p.da = reinterpret_cast<const bf16x8*>(S)[tid];
     p.id = reinterpret_cast<const uint2*>(S + 4096)[tid];
   }
+}
+
+// The wgrad role's compact stage.  Same copy as c3s_glds, but the 16-B chunks of a window change places: a lane's
+// LDS slot is fixed (wave base + 16 * lane), its source offset is not.  Window w = 4g + r keeps its 256 B of
+// values and 128 B of argmax bytes where they were; inside them value chunk c (channels 8c..8c+7) sits at slot
+// c ^ 2g and argmax chunk m (channels 16m..16m+15) at slot m ^ g.  The lanes that build m-tile m's A fragments
+// read channel 16m + lane % 16 of windows 4g + r, g = lane / 16: unswizzled, their four lane groups would meet
+// 1024 B (values) or 512 B (bytes) apart, on the same banks.  c3w_stage_off: wave-instruction k's source offset.
+__device__ __forceinline__ uint32_t c3w_stage_off(int k, int lane) {
+  if (k < 4) return (k * 64 + (lane & ~15) + ((lane & 15) ^ (2 * k))) * 16;
+  const int kk = k - 4;  // windows 8kk + lane / 8: g = 2kk + lane / 32
+  return (kk * 64 + (lane & ~7) + ((lane & 7) ^ (2 * kk + (lane >> 5)))) * 16;
+}
+__device__ __forceinline__ void c3w_stage_glds(const bf16* __restrict__ da3m, const uint8_t* __restrict__ idx3, int b,
+                                               char* S, int k, uint32_t voff) {
+  if (k < 4)
+    glds16_sv(da3m + (int64_t)b * 2048, voff, S + k * 1024);
+  else
+    glds16_sv(idx3 + (int64_t)b * 2048, voff, S + k * 1024);
+}
+
+// v_smfmac_f32_16x16x64_bf16, D[16 x 16] += A[16 x 64, 2:4 sparse] * B[64 x 16], as measured on gfx950 by
+// tools/smfmac_probe.hip (profiles/r10/c3_wgrad_sparse/probe.md); it issues at the dense 16x16x32's rate.
+//   A (8 bf16 per lane): lane l holds row l % 16.  Slots 2r, 2r+1 are the two kept values of the four dense
+//     columns k = 16 (l / 16) + 4r .. + 3, r = 0..3.
+//   index VGPR of the same lane: bits [2e+1 : 2e] = which of its four columns slot e stands for.  abid = 0 takes
+//     these 16 bits from the low half of the register, abid = 1 from the high half; cbsz is ignored.  The two
+//     indices of a group need not be ascending or distinct: every slot is simply multiplied with the B row it
+//     names (all 16 pairs checked), so one live value per group goes in slot 2r whatever its position, with a
+//     zero in slot 2r+1.
+//   B (16 bf16 per lane): lane l holds column l % 16; slots 0-7 are rows k = 8 (l / 16) + s, slots 8-15 rows
+//     32 + 8 (l / 16) + (s - 8): the B fragments of two consecutive dense 16x16x32 k-steps, back to back.
+//   D: as the dense instruction (lane l: column l % 16, rows 4 (l / 16) .. + 3).
+typedef __bf16 bf16x16 __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ f32x4 smfmac16x16x64(const bf16x8& a, const bf16x16& b, const f32x4& c, int idx) {
+  return __builtin_amdgcn_smfmac_f32_16x16x64_bf16(a, b, c, idx, 0, 0);
 }
 
 // a2 image -> C3V_XRS rows by LDS-DMA: wave-instruction k (0..15) covers LDS chunks 64k..64k+63, 10 16-B
@@ -849,11 +891,12 @@ __device__ __forceinline__ void conv3_dgrad8_role(char* smem, const bf16* __rest
 __device__ __forceinline__ void conv3_wgrad8_role(char* smem, const bf16* __restrict__ a2, const bf16* __restrict__ da3m,
                                                   const uint8_t* __restrict__ idx3, float* __restrict__ slabs, int B,
                                                   int nslices, int slice) {
-  // three D / X image buffers: image i computes from buffer i % 3 while image i+2 is staged into (i+2) % 3,
-  // so image i+1's first fragments can be read before the barrier that ends image i
-  auto Db = [&](int k) { return reinterpret_cast<bf16*>(smem + k * C3V_D); };
-  auto Xb = [&](int k) { return reinterpret_cast<bf16*>(smem + 3 * C3V_D + k * C3V_X); };
-  auto Sb = [&](int k) { return smem + 3 * (C3V_D + C3V_X) + k * C3S_B; };
+  // three X image buffers: image i computes from buffer i % 3 while image i+2 is staged into (i+2) % 3; two F
+  // buffers: image i+1's A fragments are read into registers (from F[(i+1) & 1]) while image i computes, and
+  // image i+2's are built into F[i & 1], which image i left before the barrier that ended image i-1
+  auto Xb = [&](int k) { return reinterpret_cast<bf16*>(smem + k * C3V_X); };
+  auto Fb = [&](int k) { return smem + 3 * C3V_X + k * C3V_F; };
+  auto Sb = [&](int k) { return smem + 3 * C3V_X + 2 * C3V_F + k * C3S_B; };
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   // wave (wm, wn): m-tiles (co) 4wm..4wm+3 x n-tiles 4j + wn (j < 9), n = tap*64 + ci, i.e. tap j and channels
@@ -869,79 +912,97 @@ __device__ __forceinline__ void conv3_wgrad8_role(char* smem, const bf16* __rest
   // multiples of 8 an image's two readers of the compact gradient run on one XCD at about the same time
   const int n = slice < B ? (B - slice + nslices - 1) / nslices : 0;
   auto img = [&](int i) { return slice + i * nslices; };
-  // this wave's a2 DMA instructions: k = wave, wave + 8
+  // this wave's a2 DMA instructions: k = wave, wave + 8; its compact-stage instruction: k = wave (waves 0-5)
   const uint32_t xo0 = a2_rows_off(wave, lane), xo1 = a2_rows_off(wave + 8, lane);
+  const uint32_t so = c3w_stage_off(wave < 6 ? wave : 0, lane);
   auto dma_x = [&](int b, bf16* X) {
     a2_glds_rows(a2, b, X, wave, xo0);
     a2_glds_rows(a2, b, X, wave + 8, xo1);
   };
-  auto expand = [&](const char* S, bf16* D) {
-    C3Pre pre;
-    c3s_pre(S, tid, pre);
-    c3_expand(pre, tid, [&](int r) { return D + c3v_drow(r); });
+  auto dma_s = [&](int b, char* S) {
+    if (wave < 6) c3w_stage_glds(da3m, idx3, b, S, wave, so);
   };
-  auto readA = [&](int buf, int ks, bf16x8 (&af)[4]) {
-    const bf16* D = Db(buf) + 64 * wm + 4 * p;
-    const int kb = ks * 32 + grp * 8;
+  // A operand of one image, compact stage -> F: thread (m-tile mt = wave, lane) forms the fragment and index word
+  // that lane `lane` of the MFMA waves feeds for m-tile mt.  Row co = 16 mt + lane % 16; the lane group g = lane / 16
+  // covers dense rows k = 16g..16g+15 of the window-ordered d(conv3), i.e. windows w = 4g + r (k = 4w + argmax):
+  // slot 2r = da3m[w][co], slot 2r+1 = 0 (a zero-extended 16-bit read is that pair), index field 2r = argmax[w][co].
+  // A dead window (a3 <= 0) has value 0 in both slots.
+  const int sv = grp * 1024 + (((2 * wave + (g16 >> 3)) ^ (2 * grp)) * 16) + (g16 & 7) * 2;  // + 256 r
+  const int si = 4096 + grp * 512 + ((wave ^ grp) * 16) + g16;                              // + 128 r
+  auto expand = [&](const char* S, char* F) {
+    uint32_t v[4], a[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      v[r] = *reinterpret_cast<const uint16_t*>(S + sv + 256 * r);
+      a[r] = *reinterpret_cast<const uint8_t*>(S + si + 128 * r);
+    }
+    *reinterpret_cast<uint4*>(F + (wave * 64 + lane) * 16) = make_uint4(v[0], v[1], v[2], v[3]);
+    // bits 0-1 of each byte, as c3_rows reads them
+    *reinterpret_cast<uint32_t*>(F + C3V_FV + (wave * 64 + lane) * 4) =
+        (a[0] | (a[1] << 4) | (a[2] << 8) | (a[3] << 12)) & 0x3333u;
+  };
+  auto readA = [&](int buf, bf16x8 (&af)[4], int (&ix)[4]) {
+    const char* F = Fb(buf) + (4 * wm * 64 + lane) * 16;
+    const char* I = Fb(buf) + C3V_FV + (4 * wm * 64 + lane) * 4;
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi) {
-      const bf16x4 lo = lds_read_tr16(D + c3v_drow(kb + q) + mi * 16);
-      const bf16x4 hi = lds_read_tr16(D + c3v_drow(kb + 4 + q) + mi * 16);
-      af[mi] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      af[mi] = *reinterpret_cast<const bf16x8*>(F + mi * 1024);
+      ix[mi] = *reinterpret_cast<const int*>(I + mi * 256);
     }
   };
   if (n > 0) {  // prologue: images 0 and 1 staged, image 2's compact gradient in S0
-    if (wave < 6) {
-      c3s_glds(da3m, idx3, img(0), Sb(0), wave, lane);
-      if (n > 1) c3s_glds(da3m, idx3, img(1), Sb(1), wave, lane);
-    }
+    dma_s(img(0), Sb(0));
+    if (n > 1) dma_s(img(1), Sb(1));
     dma_x(img(0), Xb(0));
     if (n > 1) dma_x(img(1), Xb(1));
     c_dma_wait();
     lds_barrier();
-    expand(Sb(0), Db(0));
-    if (n > 1) expand(Sb(1), Db(1));
+    expand(Sb(0), Fb(0));
+    if (n > 1) expand(Sb(1), Fb(1));
     lds_barrier();  // S0, S1 free
-    if (n > 2 && wave < 6) c3s_glds(da3m, idx3, img(2), Sb(0), wave, lane);
+    if (n > 2) dma_s(img(2), Sb(0));
     c_dma_wait();
   }
   lds_barrier();
-  bf16x8 af[4], afn[4];
-  if (n > 0) readA(0, 0, af);
-  for (int i = 0; i < n; ++i) {
+  bf16x8 afa[4], afb[4];
+  int ixa[4], ixb[4];
+  if (n > 0) readA(0, afa, ixa);
+  lds_barrier();  // every wave holds image 0's fragments: F0 may be rebuilt
+  // one image: af / ix are its A fragments, afn / ixn receive the next image's
+  auto image = [&](int i, const bf16x8 (&af)[4], const int (&ix)[4], bf16x8 (&afn)[4], int (&ixn)[4]) {
     const int cur = i % 3;
     const int st = (i + 2) % 3;  // staging buffer of image i+2
     if (i + 2 < n) dma_x(img(i + 2), Xb(st));
-    if (i + 3 < n && wave < 6) c3s_glds(da3m, idx3, img(i + 3), Sb((i + 1) & 1), wave, lane);
+    if (i + 3 < n) dma_s(img(i + 3), Sb((i + 1) & 1));
     const int xb = (int)(Xb(cur) - reinterpret_cast<const bf16*>(smem)) + 16 * wn + 4 * p;  // element offset
+    // B: the lane group's 16 rows are k = 8 grp .. + 7 and 32 + 8 grp .. + 7, the a2 positions of windows 2 grp,
+    // 2 grp + 1 and, four image rows (40 positions) below them, 8 + 2 grp, 8 + 2 grp + 1
+    int x0 = xb + win_pos(grp * 8 + q, 10) * C3V_XRS, x1 = xb + win_pos(grp * 8 + 4 + q, 10) * C3V_XRS;
+    // the whole per-lane part of the address opaque to the optimiser: otherwise it folds the tap offset into
+    // a per-tap SGPR or VGPR and pays one VALU add per fragment read instead of the immediate offset
+    asm("" : "+v"(x0), "+v"(x1));
+    const bf16* S0 = reinterpret_cast<const bf16*>(smem);
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int kb = ks * 32 + grp * 8;
-      int x0 = xb + win_pos(kb + q, 10) * C3V_XRS, x1 = xb + win_pos(kb + 4 + q, 10) * C3V_XRS;
-      // the whole per-lane part of the address opaque to the optimiser: otherwise it folds the tap offset into
-      // a per-tap SGPR or VGPR and pays one VALU add per fragment read instead of the immediate offset
-      asm("" : "+v"(x0), "+v"(x1));
-      const bf16* S0 = reinterpret_cast<const bf16*>(smem);
+    for (int j = 0; j < 9; ++j) {
+      const int shift = ((j / 3) * 10 + j % 3) * C3V_XRS;  // tap j
+      const bf16x4 b0 = lds_read_tr16(S0 + x0 + shift);
+      const bf16x4 b1 = lds_read_tr16(S0 + x1 + shift);
+      const bf16x4 b2 = lds_read_tr16(S0 + x0 + shift + 40 * C3V_XRS);
+      const bf16x4 b3 = lds_read_tr16(S0 + x1 + shift + 40 * C3V_XRS);
+      const bf16x16 bf = bf16x16{b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3],
+                                 b2[0], b2[1], b2[2], b2[3], b3[0], b3[1], b3[2], b3[3]};
+      if (j == 2 && i + 2 < n) expand(Sb(i & 1), Fb(i & 1));  // image i+2's A operand
+      if (j == 5 && i + 1 < n) readA((i + 1) & 1, afn, ixn);  // image i+1's: its buffer is complete
 #pragma unroll
-      for (int j = 0; j < 9; ++j) {
-        const int shift = ((j / 3) * 10 + j % 3) * C3V_XRS;  // tap j
-        const bf16x4 lo = lds_read_tr16(S0 + x0 + shift);
-        const bf16x4 hi = lds_read_tr16(S0 + x1 + shift);
-        const bf16x8 bf = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        if (j == 4) {  // next k-step's A fragments (image i+1's first, when ks = 1: its buffer is complete)
-          if (ks == 0)
-            readA(cur, 1, afn);
-          else if (i + 1 < n)
-            readA((i + 1) % 3, 0, af);
-        }
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi) acc[mi][j] = mfma16x16x32(ks == 0 ? af[mi] : afn[mi], bf, acc[mi][j]);
-      }
-      if (ks == 0 && i + 2 < n) expand(Sb(i & 1), Db(st));  // image i+2's D, under the second k-step
+      for (int mi = 0; mi < 4; ++mi) acc[mi][j] = smfmac16x16x64(af[mi], bf, acc[mi][j], ix[mi]);
     }
     // (letting image i+2's a2 copies stay in flight across the barrier measured 50 us slower)
     c_dma_wait();
     lds_barrier();
+  };
+  for (int i = 0; i < n; i += 2) {  // two images per trip: the fragment registers swap roles without moves
+    image(i, afa, ixa, afb, ixb);
+    if (i + 1 < n) image(i + 1, afb, ixb, afa, ixa);
   }
   float* slab = slabs + (int64_t)slice * C3_WSLAB;
 #pragma unroll
@@ -991,16 +1052,19 @@ __global__ __launch_bounds__(512, 1) void conv3_bwd8_kernel(const bf16* __restri
 }  // namespace
 
 // Work split of the role-fused backward launches.  All blocks of a launch are co-resident (one
-// 512-thread block per CU), so dgrad and wgrad blocks are sized to finish together: dgrad does
-// ~2x (conv3) / ~1.25x (conv2) the MFMA work of wgrad per image.
+// 512-thread block per CU), so dgrad and wgrad blocks are sized to finish together.
 // RINGDP_C*_DGRAD_FRAC override the measured fraction of the CUs given to the dgrad role (tuning sweeps),
 // RINGDP_C*_WMIN the fewest images per weight-gradient slab (small batches: more slabs = more reduction traffic).
-// dgrad and wgrad do about the same MFMA work per image (624 / 576 MFMAs); measured best split 0.5-0.6 of
-// the workgroup slots (B=32768).
+// conv3, 8-wave kernel: a dgrad image is 624 MFMAs plus the pool2 backward, about 5300 cycles of a workgroup; a
+// wgrad image is 288 sparse MFMAs, about 2700 (3900 as 576 dense ones), so the dgrad role gets two CUs in three.
+// B=65536, conv3 + fc1 backward, two interleaved passes: 1077-1080 us at 0.66, 1164-1173 at the dense role's
+// 0.55, 1085-1111 at 0.59-0.63, 1068-1079 at 0.69 without the steal (profiles/r10/c3_wgrad_sparse/README.md).
+// conv3, 4-wave kernel: dgrad and wgrad do about the same MFMA work per image (624 / 576 MFMAs); measured best
+// split 0.5-0.6 of the workgroup slots (B=32768, when it still served that batch).
 static void c3_split(int B, bool dgrad, int& nd, int& ws) {
   if (use_8wave(B)) {  // one 512-thread workgroup per CU; ws = wgrad slices, one workgroup each
     const int cus = num_cus();
-    static const double frac = env_real("RINGDP_C3_DGRAD_FRAC", 0.55, split_frac_ok);
+    static const double frac = env_real("RINGDP_C3_DGRAD_FRAC", 0.66, split_frac_ok);
     nd = clampi(((int)(frac * cus) + 4) / 8 * 8, 8, cus - 8);  // multiples of 8: see conv3_wgrad8_role
     ws = clampi(cdiv(B, 8), 1, cus - nd);
     // Without a data gradient the same slices, on as many workgroups, and no dgrad workgroups: a slice is a
@@ -1026,10 +1090,11 @@ static void c3_split(int B, bool dgrad, int& nd, int& ws) {
 
 // Images [0, result) of the conv3 data gradient run on the dgrad workgroups, the rest on the wgrad
 // workgroups after their weight-gradient slice (RINGDP_C3_STEAL = that share; large batches only, where
-// each dgrad workgroup has many images).  0.04 since the dgrad role's image takes 10 % fewer cycles (pool2
-// backward on all four helper waves, helper waves ahead at the issue port): conv3 + fc1 backward at B=65536,
-// three passes each, 1166-1175 us at 0.04, 1172-1178 at 0.05, 1178-1183 at 0.03, 1191-1198 at 0.07, the
-// parent kernel 1209-1215 (profiles/r07/c3_dgrad/README.md).  0.07 had replaced 0.1 for the old role
+// each dgrad workgroup has many images).  The share evens out what the 8-workgroup steps of the split leave:
+// with the sparse weight gradient and 0.66 of the CUs on the dgrad role, conv3 + fc1 backward at B=65536 is flat
+// within its run-to-run spread (about 13 us) from 0.01 to 0.04: 1083-1089 us at 0.01, 1071-1084 at 0.02, 1077-1080
+// at 0.04, 1082-1096 without (profiles/r10/c3_wgrad_sparse/README.md), so 0.04 stays.  It had been fitted to the
+// dense role at 0.55 (profiles/r07/c3_dgrad/README.md), and 0.07 / 0.1 to the roles before that
 // (profiles/r06/c3_steal_sweep.txt).
 static int c3_dgrad_images(int B, int nd) {
   static const double steal = env_real("RINGDP_C3_STEAL", 0.04, [](double f) { return f >= 0.0 && f < 0.9; });
