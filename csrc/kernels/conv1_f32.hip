@@ -1,5 +1,5 @@
 // The ConvNet's first layer at fp32 (ref/launch_dist.py:35-41: conv1 1->32, 5x5, pad 1 on 28x28, ReLU,
-// 2x2/s2 max-pool), as two dedicated kernels instead of implicit GEMMs (csrc/kernels/conv_f32.hip).
+// 2x2/s2 max-pool), as two dedicated kernels instead of implicit GEMMs (csrc/kernels/conv_f32_gemm.h).
 //
 // With one input channel the implicit GEMM's operand gathers cost far more than its 25-deep
 // products (PMC: the generic kernel ran at ~22 TF/s, the pool1 passes another 3 ms per step at
@@ -12,7 +12,7 @@
 //   * weight gradient: D[n][tap] = sum_p dz1[n][p] x img[p + tap] over the wave's images, with
 //     dz1 decoded on the fly from the pooled gradient and the code (the pool1 backward pass is
 //     gone), column 25 of the B operand = 1 so the bias gradient is the same MFMA; per-workgroup
-//     partials in a fixed order into a slab that the conv_f32 slab reduction sums.
+//     partials in a fixed order into a slab that the conv_f32_wgrad.hip slab reduction sums.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

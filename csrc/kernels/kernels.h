@@ -142,7 +142,7 @@ struct XgArgs {
 };
 void xgmi_collective(const XgArgs& a, hipStream_t s);
 
-// ---------------------------------------------------------------- fp32 NCHW conv / pool (conv_f32.hip)
+// ---------------------------------------------------------------- fp32 NCHW conv / pool (conv_f32_*.hip)
 // stride-1 conv, square kernel R, symmetric zero padding; fc layers are R=1 convs over 1x1 images
 struct ConvF32Geom {
   int64_t B;
@@ -167,7 +167,7 @@ void conv_f32_fwd_pool_split(const ConvF32Geom& g, const float* x, const float* 
 // slab: conv_f32_dgrad_slices(g) x B*C*H*W floats of split-K partials when that count is > 1 (else unused)
 int conv_f32_dgrad_slices(const ConvF32Geom& g);
 // The ConvNet's conv3 (128 -> 64 channels, 8x8 -> 10x10) and conv2 (64 -> 32, 11x11 -> 13x13) data gradients
-// over the live taps only (scatter form, conv_f32.hip); ok: one of these geometries and a batch of at least two
+// over the live taps only (scatter form, conv_f32_dgrad.hip); ok: one of these geometries and a batch of at least two
 // images per CU; wp: conv_dgrad_f32_scratch() floats
 bool conv_dgrad_f32_scatter_ok(const ConvF32Geom& g);
 int conv_dgrad_f32_scratch();

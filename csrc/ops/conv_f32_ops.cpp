@@ -1,5 +1,6 @@
-// Tensor-level wrappers for the fp32 NCHW conv / pool kernels (csrc/kernels/conv_f32.hip): the
-// ConvNet at the reference's fp32 precision (ringdp/ops/convnet_fp32.py).
+// Tensor-level wrappers for the fp32 NCHW conv / pool kernels (csrc/kernels/conv_f32_fwd.hip, conv_f32_dgrad.hip,
+// conv_f32_wgrad.hip, conv_f32_pool.hip, conv1_f32.hip): the ConvNet at the reference's fp32 precision
+// (ringdp/ops/convnet_fp32.py).
 #include <torch/extension.h>
 
 #include "../kernels/kernels.h"
@@ -27,6 +28,21 @@ kern::ConvF32Geom geom(const at::Tensor& x, const at::Tensor& w, int64_t pad) {
   g.OH = g.H + 2 * g.pad - g.R + 1;
   g.OW = g.W + 2 * g.pad - g.R + 1;
   RINGDP_CHECK(g.OH > 0 && g.OW > 0, "conv_f32: empty output");
+  return g;
+}
+
+// the geometry of a data gradient: batch and output size from dz, channels and kernel from w
+kern::ConvF32Geom geom_from_dz(const at::Tensor& dz, const at::Tensor& w, int64_t H, int64_t W, int64_t pad) {
+  kern::ConvF32Geom g;
+  g.B = dz.size(0);
+  g.Kout = static_cast<int>(w.size(0));
+  g.C = static_cast<int>(w.size(1));
+  g.R = static_cast<int>(w.size(2));
+  g.H = static_cast<int>(H);
+  g.W = static_cast<int>(W);
+  g.pad = static_cast<int>(pad);
+  g.OH = g.H + 2 * g.pad - g.R + 1;
+  g.OW = g.W + 2 * g.pad - g.R + 1;
   return g;
 }
 
@@ -154,16 +170,7 @@ void f32_conv1_wgrad(const at::Tensor& x, const at::Tensor& da1, const at::Tenso
 at::Tensor f32_conv_dgrad(const at::Tensor& dz, const at::Tensor& w, int64_t H, int64_t W, int64_t pad) {
   util::f32_gpu(dz, "conv_f32 dz");
   util::f32_gpu(w, "conv_f32 weight");
-  kern::ConvF32Geom g;
-  g.B = dz.size(0);
-  g.Kout = static_cast<int>(w.size(0));
-  g.C = static_cast<int>(w.size(1));
-  g.R = static_cast<int>(w.size(2));
-  g.H = static_cast<int>(H);
-  g.W = static_cast<int>(W);
-  g.pad = static_cast<int>(pad);
-  g.OH = g.H + 2 * g.pad - g.R + 1;
-  g.OW = g.W + 2 * g.pad - g.R + 1;
+  const auto g = geom_from_dz(dz, w, H, W, pad);
   RINGDP_CHECK(dz.dim() == 4 && dz.size(1) == g.Kout && dz.size(2) == g.OH && dz.size(3) == g.OW,
                "conv_f32 dgrad: dz has shape ", dz.sizes());
   auto dx = at::empty({g.B, g.C, g.H, g.W}, dz.options());
@@ -213,16 +220,8 @@ void f32_conv_wgrad(const at::Tensor& dz, const at::Tensor& x, int64_t pad, doub
 at::Tensor f32_conv_dgrad_pool2s1_bwd(const at::Tensor& dz, const at::Tensor& w, const at::Tensor& code) {
   util::f32_gpu(dz, "conv_f32 dz");
   util::f32_gpu(w, "conv_f32 weight");
-  kern::ConvF32Geom g;
-  g.B = dz.size(0);
-  g.Kout = static_cast<int>(w.size(0));
-  g.C = static_cast<int>(w.size(1));
-  g.R = static_cast<int>(w.size(2));
-  g.pad = 0;
-  g.OH = static_cast<int>(dz.size(2));
-  g.OW = static_cast<int>(dz.size(3));
-  g.H = g.OH + g.R - 1;
-  g.W = g.OW + g.R - 1;
+  // a valid conv: the input is R - 1 larger than dz
+  const auto g = geom_from_dz(dz, w, dz.size(2) + w.size(2) - 1, dz.size(3) + w.size(2) - 1, 0);
   RINGDP_CHECK(dz.dim() == 4 && dz.size(1) == g.Kout && dz.is_contiguous() && w.is_contiguous(),
                "conv_f32 dgrad + pool: dz has shape ", dz.sizes());
   RINGDP_CHECK(code.scalar_type() == at::kByte && code.dim() == 4 && code.size(0) == g.B && code.size(1) == g.C &&

@@ -1,6 +1,7 @@
 """The MNIST ConvNet at the reference's fp32 precision (ref/launch_dist.py:50-59).
 
-Layer-by-layer autograd Functions over the exact-f32 MFMA kernels of csrc/kernels/conv_f32.hip:
+Layer-by-layer autograd Functions over the exact-f32 MFMA kernels of csrc/kernels/conv_f32_fwd.hip,
+conv_f32_dgrad.hip, conv_f32_wgrad.hip, conv_f32_pool.hip and conv1_f32.hip:
 conv (implicit GEMM; fc1 runs as a 1x1 conv over the flattened 2048-vector), and ReLU fused into
 max-pool with a 1-byte argmax code (backward is a gather, deterministic also for the overlapping
 2x2/s1 pool2).  Every conv runs ReLU + its pool inside the conv launch (conv1: a dedicated one-wave-

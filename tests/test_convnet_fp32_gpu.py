@@ -229,7 +229,7 @@ def _models(seed=0):
 @pytest.mark.parametrize("B", [64, 2048])
 def test_fp32_convnet_matches_aten(B):
     """Forward + gradients of the fp32 model against ATen fp32.  B=2048 runs the large-batch kernels of
-    csrc/kernels/conv_f32.hip in the model (scatter data gradients, dedicated weight gradients, the conv2 / conv3
+    csrc/kernels/conv_f32_*.hip in the model (scatter data gradients, dedicated weight gradients, the conv2 / conv3
     + pool forwards, the tiled pool2 backward); B=64 the small-batch split-K path."""
     m32, ref = _models()
     x = torch.randint(0, 256, (B, 1, 28, 28), dtype=torch.uint8, device=DEV)
@@ -252,12 +252,13 @@ def test_fp32_convnet_matches_aten(B):
             assert rel < 5e-3, (n, rel)
 
 
-@pytest.mark.parametrize("B", [100, 700])
+@pytest.mark.parametrize("B", [100, 700, 2048])
 def test_fp32_net_node_matches_per_layer_backward(B):
     """ringdp's cross entropy on the fp32 model at a small batch is ONE node over the whole network (one
     weight-gradient reduction launch; cross entropy + fc1 data gradient + pool3 backward fused).  The loss and fc1's
     gradients (same logits gradient, same GEMM, same fixed-order reduction) equal the per-layer backward's bit for
-    bit; the conv layers' to fp32 rounding (fc1's data gradient is an fmaf chain instead of the GEMM's MFMAs)."""
+    bit; the conv layers' to fp32 rounding (fc1's data gradient is an fmaf chain instead of the GEMM's MFMAs).
+    B=2048: the node defers the dedicated conv2 / conv3 weight-gradient kernels' slabs to the one reduction launch."""
     from ringdp.ops.loss import _CrossEntropy, cross_entropy
 
     m_a, _ = _models(3)
@@ -342,7 +343,7 @@ def test_convergence_200_steps_fp32_and_bf16(B):
 @pytest.mark.parametrize("B", [600, 1024])
 @pytest.mark.parametrize("Cin,H,K", [(64, 10, 128), (32, 13, 64)])
 def test_conv_dgrad_f32_scatter(B, Cin, H, K):
-    """conv3's and conv2's data gradients over the live taps only (scatter form, csrc/kernels/conv_f32.hip
+    """conv3's and conv2's data gradients over the live taps only (scatter form, csrc/kernels/conv_f32_dgrad.hip
     conv3_dgrad_f32_kernel / conv2_dgrad_f32_kernel: batches of at least 2 images per CU) against fp64,
     against the implicit-GEMM path that 100-image batches take (same values up to summation order), and
     bit-identical across runs."""
@@ -360,7 +361,7 @@ def test_conv_dgrad_f32_scatter(B, Cin, H, K):
 @pytest.mark.parametrize("B", [1024, 1500])
 @pytest.mark.parametrize("Cin,H,K", [(64, 10, 128), (32, 13, 64)])
 def test_conv_wgrad_f32_dedicated(B, Cin, H, K):
-    """conv3's and conv2's weight + bias gradients on the dedicated kernels (csrc/kernels/conv_f32.hip
+    """conv3's and conv2's weight + bias gradients on the dedicated kernels (csrc/kernels/conv_f32_wgrad.hip
     conv3_wgrad_f32_kernel / conv2_wgrad_f32_kernel: 128 image slices x the 16-channel tiles, slab + fixed-order
     reduction) against fp64 and bit-identical across runs."""
     g = torch.Generator(device=DEV).manual_seed(B + K)
@@ -382,7 +383,7 @@ def test_conv_wgrad_f32_dedicated(B, Cin, H, K):
 @pytest.mark.parametrize("B", [1024, 1100])
 def test_conv2_pool_f32_dedicated(B):
     """conv2 + bias + ReLU + overlapping 2x2/s1 max-pool on the dedicated forward kernel
-    (csrc/kernels/conv_f32.hip conv2_pool_f32_kernel: batches of >= 4 images per CU) against fp64: pooled
+    (csrc/kernels/conv_f32_fwd.hip conv2_pool_f32_kernel: batches of >= 4 images per CU) against fp64: pooled
     values, and the argmax codes wherever the window's maximum is not a near-tie."""
     g = torch.Generator(device=DEV).manual_seed(B + 5)
     x = torch.randn(B, 32, 13, 13, device=DEV, generator=g)
@@ -405,7 +406,7 @@ def test_conv2_pool_f32_dedicated(B):
 
 @pytest.mark.parametrize("B", [1024, 1100])
 def test_conv3_pool_f32_dedicated(B):
-    """conv3 + bias + ReLU + 2x2/s2 max-pool on the dedicated forward kernel (csrc/kernels/conv_f32.hip
+    """conv3 + bias + ReLU + 2x2/s2 max-pool on the dedicated forward kernel (csrc/kernels/conv_f32_fwd.hip
     conv3_pool_f32_kernel: weights resident in 8 waves' registers, window-major m-tiles pooled in registers)
     against fp64: pooled values, argmax codes wherever the window maximum is not a near-tie, dead windows 255,
     and against the implicit-GEMM path at a batch below the dedicated kernel's threshold."""
@@ -431,7 +432,7 @@ def test_conv3_pool_f32_dedicated(B):
 
 @pytest.mark.parametrize("planes,H", [((64, 64), 11), ((4, 8), 9), ((3, 5), 11)])
 def test_pool2s1_bwd_tile_matches_elementwise(planes, H):
-    """The LDS-tiled overlapping-pool backward (csrc/kernels/conv_f32.hip pool2s1_bwd_tile_kernel, 16 planes per
+    """The LDS-tiled overlapping-pool backward (csrc/kernels/conv_f32_pool.hip pool2s1_bwd_tile_kernel, 16 planes per
     tile) against autograd through max_pool2d: (64, 64) planes take the tiled path with the compile-time 10 x 10
     window grid, 9 x 9 inputs its runtime-size variant, (3, 5) = 15 planes the per-element kernel."""
     n, c = planes
