@@ -581,6 +581,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("head_fwd", &ops::head_fwd);
   m.def("head_bwd", &ops::head_bwd);
   m.def("add_bf16", &ops::add_bf16);
+  m.def("rng_tick", &ops::rng_tick, "dropout generator: state.step += 1 on the device, returns {seed, step}",
+        py::arg("state"));
+  m.def("dropout_bf16", &ops::dropout_bf16, "y = m * x with the Philox mask of (snapshot, site); also its own backward",
+        py::arg("x"), py::arg("snapshot"), py::arg("site"), py::arg("thr"), py::arg("site_r") = 0,
+        py::arg("thr_r") = 0, py::arg("T") = 0);
+  m.def("dropout_add_bf16", &ops::dropout_add_bf16, "y = res + m_row * m_elem * x, rounded to bf16 once",
+        py::arg("x"), py::arg("res"), py::arg("snapshot"), py::arg("site_e"), py::arg("thr_e"), py::arg("site_r"),
+        py::arg("thr_r"), py::arg("T"));
   m.def("layernorm_fwd", &ops::layernorm_fwd);
   m.def("layernorm_bwd", &ops::layernorm_bwd);
   m.def("layernorm_fwd_q8", &ops::layernorm_fwd_q8, "layernorm forward with e4m3 outputs (q, q^T) at a delayed scale");

@@ -619,6 +619,20 @@ void assemble_tokens_bwd(const void* dout, int B, int NP, int D, void* dpatches,
 void cls_rows(const void* x, int B, int T, int D, void* y, bool reverse, hipStream_t s);
 void patchify(const void* x, bool x_bf16, int B, int C, int H, int W, int P, void* out, hipStream_t s);
 
+// ---------------------------------------------------------------- dropout / stochastic depth (dropout.hip)
+// Counter-based masks (Philox4x32-10, philox.h): key = seed, counter = (group, step lo, step hi, site).  No mask
+// is stored: the backward regenerates it from the same snapshot and site.  No atomics, counters or fences.
+// state = {seed, step} in device memory: step += 1, snapshot <- {seed, step} (one thread).
+void rng_tick(uint64_t* state, uint64_t* snapshot, hipStream_t s);
+// bf16 streams of n elements (n % 8 == 0, 16-byte aligned), m = m_row * m_elem:
+//   m_elem  per element; group = index / 8, one 16-bit draw per element: draw >= thr_e ? 65536 / (65536 - thr_e) : 0
+//   m_row   per sample of row_elems consecutive elements; group = sample, same rule with thr_r
+// a threshold of 0 switches its factor off (at least one must be on).
+//   res == nullptr:  y = m ? bf16(m * x) : +0        (also the backward of both forms: dx = m * dy)
+//   res != nullptr:  y = m ? bf16(res + m * x) : res
+void dropout_bf16(const void* x, const void* res, const uint64_t* snapshot, uint32_t site_e, uint32_t thr_e,
+                  uint32_t site_r, uint32_t thr_r, int64_t row_elems, int64_t n, void* y, hipStream_t s);
+
 // ---------------------------------------------------------------- data
 // Gather B samples of a uint8 (N, H, W, C) dataset by index, random-crop (zero pad) + h-flip, then
 // ToTensor + Normalize; out_kind 0 = fp32, 1 = bf16, 2 = uint8 (no normalisation).  Output NCHW

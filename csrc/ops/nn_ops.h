@@ -50,6 +50,16 @@ at::Tensor head_bwd(const c10::optional<at::Tensor>& dl, const c10::optional<at:
                     const at::Tensor& w, int64_t H, int64_t W, at::Tensor dw, at::Tensor db);
 at::Tensor add_bf16(const at::Tensor& a, const at::Tensor& b);
 
+// Dropout / stochastic depth (dropout_ops.cpp).  state: int64 [2] = {seed, step} on the device; rng_tick advances
+// the step in place and returns a fresh int64 [2] snapshot that every dropout site of one forward and its
+// backward reads.  thr = round(p * 65536) clamped to [0, 65535]; a row-mode site (site_r, thr_r) covers T rows.
+at::Tensor rng_tick(at::Tensor state);
+// With both thresholds 0 nothing is drawn (snapshot may be absent): x itself / add_bf16(x, res).
+at::Tensor dropout_bf16(const at::Tensor& x, const c10::optional<at::Tensor>& snapshot, int64_t site, int64_t thr,
+                        int64_t site_r, int64_t thr_r, int64_t T);
+at::Tensor dropout_add_bf16(const at::Tensor& x, const at::Tensor& res, const c10::optional<at::Tensor>& snapshot,
+                            int64_t site_e, int64_t thr_e, int64_t site_r, int64_t thr_r, int64_t T);
+
 std::tuple<at::Tensor, at::Tensor> layernorm_fwd(const at::Tensor& x, const at::Tensor& w, const at::Tensor& b,
                                                  double eps);
 // LayerNorm forward writing e4m3 (delayed scaling, hist = [amax, per-64-row-block maxima]): [stats, q, qt, scale]

@@ -10,7 +10,8 @@ over xGMI:
 * ``ringdp.data``         - DistributedSampler (+ on-device variants), datasets, transforms
 * ``ringdp.multiprocessing.spawn`` / ``python -m ringdp.run`` / ``python -m ringdp.launch``
 * ``ringdp.models``       - ConvNet (MNIST) on fused MFMA kernels; ResNet / ViT families
-* ``ringdp.nn`` / ``ringdp.optim`` - cross entropy, fused SGD
+* ``ringdp.nn`` / ``ringdp.optim`` - cross entropy, dropout, fused SGD / AdamW
+* ``ringdp.random``       - device-resident generator state of the dropout masks (hipGraph-safe)
 """
 from . import distributed  # noqa: F401
 from ._native import C as _C  # noqa: F401
@@ -30,6 +31,6 @@ from .distributed import (  # noqa: F401
 )
 from .multiprocessing import spawn  # noqa: F401
 from .parallel import DistributedDataParallel  # noqa: F401
-from . import models, nn, ops, optim  # noqa: F401,E402
+from . import models, nn, ops, optim, random  # noqa: F401,E402
 
 __version__ = "0.1.0"

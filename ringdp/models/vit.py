@@ -9,6 +9,14 @@ GPU path (``forward`` on CUDA tensors): token rows are bf16 ``[B*T, 768]``; each
 LN -> fused QKV GEMM (+bias) -> attention (batched MFMA GEMMs + softmax kernel) -> out-proj GEMM
 with the residual add in its epilogue -> LN -> MLP-1 GEMM with bias+GELU epilogue (pre-activation
 kept) -> MLP-2 GEMM with the residual add in its epilogue.  CPU path: plain ATen modules.
+
+Regularisation (``dropout``, ``stochastic_depth_prob``; training mode only): dropout sits where torchvision puts
+it - after tokens + position embedding, after GELU, and on each residual branch - and stochastic depth (DeiT's
+drop-path, per-layer probability ``p * l / (L - 1)``) drops both residual branches of a block per sample.  On the
+GPU the masks come from ``ringdp.ops.dropout`` (one ``rng_tick`` per forward, hipGraph-safe), the residual add,
+the dropout and the drop-path of a branch are one kernel, and the block takes the unfused linears instead of
+MLPF / MLPF8, which costs the separate GELU-backward pass.  With everything at 0, or in ``eval()``, the path and
+the launches are the ones described above.
 """
 from __future__ import annotations
 
@@ -18,8 +26,10 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 
+from ..ops.dropout import DropoutF, drop_path_rows, drop_path_schedule, dropout_add, quantize_p
 from ..ops.transformer import (AttentionF, ClassRowsF, LayerNormF, LayerNormFork, MLPF, MLPF8, PatchTokensF,
                                 cast_weights, clear_weights, fp8_enabled, fp8_mlp_fusable, layernorm_fork, linear)
+from ..random import Draw
 
 
 class MLPBlock(nn.Sequential):
@@ -33,9 +43,11 @@ class MLPBlock(nn.Sequential):
 
 
 class EncoderBlock(nn.Module):
-    def __init__(self, heads: int, dim: int, mlp_dim: int, dropout: float = 0.0, attention_dropout: float = 0.0):
+    def __init__(self, heads: int, dim: int, mlp_dim: int, dropout: float = 0.0, attention_dropout: float = 0.0,
+                 drop_path: float = 0.0):
         super().__init__()
         self.num_heads = heads
+        self.drop_path = float(drop_path)  # stochastic depth: both residual branches, per sample
         self.ln_1 = nn.LayerNorm(dim, eps=1e-6)
         self.self_attention = nn.MultiheadAttention(dim, heads, dropout=attention_dropout, batch_first=True)
         self.dropout = nn.Dropout(dropout)
@@ -45,10 +57,47 @@ class EncoderBlock(nn.Module):
     def forward(self, x):  # ATen path, x [B, T, D]
         h = self.ln_1(x)
         h, _ = self.self_attention(h, h, h, need_weights=False)
+        if self.training and self.drop_path > 0.0:
+            x = x + drop_path_rows(self.dropout(h), self.drop_path, True)
+            return x + drop_path_rows(self.mlp(self.ln_2(x)), self.drop_path, True)
         x = x + self.dropout(h)
         return x + self.mlp(self.ln_2(x))
 
-    def forward_rows(self, x, B: int, T: int):  # ringdp path, x [B*T, D] bf16
+    def _regularised(self) -> bool:
+        """Whether forward_rows takes the dropout path: decided on the quantised thresholds the kernels use, so a
+        probability too small to drop anything (below 2^-17) keeps the fused path."""
+        return self.training and bool(quantize_p(self.dropout.p)[0] or quantize_p(self.drop_path)[0]
+                                      or self.self_attention.dropout > 0.0)
+
+    def forward_rows_dropout(self, x, B: int, T: int, draw=None):
+        """The training path with dropout and / or stochastic depth: unfused linears with the residual add, the
+        dropout and the drop-path of each branch in one kernel (DropoutAddF).  Sites in call order: out-proj
+        branch (element, then row), GELU output, fc2 branch (element, then row); a factor that is off takes no
+        site.  ``draw``: the forward's ``ringdp.random.Draw``; a block called on its own makes one."""
+        att = self.self_attention
+        if att.dropout > 0.0:
+            raise NotImplementedError("EncoderBlock: attention_dropout > 0 is not supported on the GPU path "
+                                      "(the fused attention kernels have no dropout)")
+        p, dp = self.dropout.p, self.drop_path
+        thr = quantize_p(p)[0]
+        if draw is None and (thr or quantize_p(dp)[0]):
+            draw = Draw(x.device)
+        fc1, fc2 = self.mlp[0], self.mlp[3]
+        # layernorm_fork: LayerNormFork on the bf16 path, the e4m3-writing fork for fp8 linears
+        h, x = layernorm_fork(x, self.ln_1, att.in_proj_weight)
+        qkv = _lin(h, att.in_proj_weight, att.in_proj_bias)
+        o = AttentionF.apply(qkv, B, T, self.num_heads)
+        h = linear(o, att.out_proj)  # no residual in the epilogue
+        x = dropout_add(h, x, p, True, draw, dp, T)
+        h, x = layernorm_fork(x, self.ln_2, fc1.weight)
+        a = linear(h, fc1, act=2)
+        if thr:
+            a = DropoutF.apply(a, draw.snapshot, draw.site(), thr)
+        return dropout_add(linear(a, fc2), x, p, True, draw, dp, T)
+
+    def forward_rows(self, x, B: int, T: int, draw=None):  # ringdp path, x [B*T, D] bf16
+        if self._regularised():
+            return self.forward_rows_dropout(x, B, T, draw)
         att = self.self_attention
         if fp8_enabled():  # fp8 linears (LinearF's quantised path); residual gradients join in the LN backward
             fc1, fc2 = self.mlp[0], self.mlp[3]
@@ -80,12 +129,13 @@ def _lin(x, w, b):
 
 class Encoder(nn.Module):
     def __init__(self, seq_length: int, num_layers: int, heads: int, dim: int, mlp_dim: int, dropout: float = 0.0,
-                 attention_dropout: float = 0.0):
+                 attention_dropout: float = 0.0, stochastic_depth_prob: float = 0.0):
         super().__init__()
         self.pos_embedding = nn.Parameter(torch.empty(1, seq_length, dim).normal_(std=0.02))
         self.dropout = nn.Dropout(dropout)
+        dps = drop_path_schedule(stochastic_depth_prob, num_layers)
         self.layers = nn.Sequential(OrderedDict(
-            (f"encoder_layer_{i}", EncoderBlock(heads, dim, mlp_dim, dropout, attention_dropout))
+            (f"encoder_layer_{i}", EncoderBlock(heads, dim, mlp_dim, dropout, attention_dropout, dps[i]))
             for i in range(num_layers)))
         self.ln = nn.LayerNorm(dim, eps=1e-6)
 
@@ -95,13 +145,15 @@ class Encoder(nn.Module):
 
 class VisionTransformer(nn.Module):
     def __init__(self, image_size: int = 224, patch_size: int = 16, num_layers: int = 12, num_heads: int = 12,
-                 hidden_dim: int = 768, mlp_dim: int = 3072, num_classes: int = 1000, dropout: float = 0.0):
+                 hidden_dim: int = 768, mlp_dim: int = 3072, num_classes: int = 1000, dropout: float = 0.0,
+                 stochastic_depth_prob: float = 0.0):
         super().__init__()
         self.image_size, self.patch_size, self.hidden_dim = image_size, patch_size, hidden_dim
         self.conv_proj = nn.Conv2d(3, hidden_dim, kernel_size=patch_size, stride=patch_size)
         seq_length = (image_size // patch_size) ** 2 + 1
         self.class_token = nn.Parameter(torch.zeros(1, 1, hidden_dim))
-        self.encoder = Encoder(seq_length, num_layers, num_heads, hidden_dim, mlp_dim, dropout)
+        self.encoder = Encoder(seq_length, num_layers, num_heads, hidden_dim, mlp_dim, dropout,
+                               stochastic_depth_prob=stochastic_depth_prob)
         self.seq_length = seq_length
         self.heads = nn.Sequential(OrderedDict(head=nn.Linear(hidden_dim, num_classes)))
         fan_in = 3 * patch_size * patch_size
@@ -133,8 +185,17 @@ class VisionTransformer(nn.Module):
         try:
             h = PatchTokensF.apply(x, self.conv_proj.weight, self.conv_proj.bias, self.class_token,
                                    self.encoder.pos_embedding, self.patch_size)
-            for blk in self.encoder.layers:
-                h = blk.forward_rows(h, B, T)
+            if self.training and any(blk._regularised() for blk in self.encoder.layers):
+                # one tick for the whole forward; site 0 is the embedding dropout, then each block's sites in order
+                draw = Draw(x.device)
+                thr = quantize_p(self.encoder.dropout.p)[0]
+                if thr:
+                    h = DropoutF.apply(h, draw.snapshot, draw.site(), thr)
+                for blk in self.encoder.layers:
+                    h = blk.forward_rows(h, B, T, draw)
+            else:
+                for blk in self.encoder.layers:
+                    h = blk.forward_rows(h, B, T)
         finally:
             clear_weights()
         ln = self.encoder.ln

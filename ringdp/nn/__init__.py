@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import torch.nn as _nn
 
+from ..ops.dropout import dropout
 from ..ops.loss import cross_entropy
 from . import utils  # noqa: F401  (ringdp.nn.utils.clip_grad_norm_)
 
@@ -26,4 +27,26 @@ class CrossEntropyLoss(_nn.Module):
         return cross_entropy(input, target, self.ignore_index, self.label_smoothing, self.reduction)
 
 
-__all__ = ["CrossEntropyLoss", "cross_entropy"]
+class Dropout(_nn.Module):
+    """Drop-in for ``torch.nn.Dropout`` on bf16 GPU rows (``ringdp.ops.dropout``): counter-based masks from the
+    device-resident ``ringdp.random`` state, regenerated in the backward (no stored mask), hipGraph-safe.  CPU
+    tensors go to ATen; other dtypes on the GPU raise.  One difference on the GPU: ``p`` is quantised to a 16-bit
+    threshold clamped to 65535, so ``p = 1`` keeps each element with probability 2^-16 (scaled by 65536) where ATen
+    zeroes everything; every ``p <= 1 - 2^-16`` is realised to within 2^-17."""
+
+    def __init__(self, p: float = 0.5, inplace: bool = False):
+        super().__init__()
+        if inplace:
+            raise NotImplementedError("ringdp.nn.Dropout: inplace is not supported")
+        if not 0.0 <= p <= 1.0:
+            raise ValueError(f"dropout probability has to be between 0 and 1, but got {p}")
+        self.p = p
+
+    def forward(self, input, draw=None):
+        return dropout(input, self.p, self.training, draw)
+
+    def extra_repr(self) -> str:
+        return f"p={self.p}"
+
+
+__all__ = ["CrossEntropyLoss", "Dropout", "cross_entropy", "dropout"]
