@@ -542,6 +542,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grad_scale_run", &ops::grad_scale_run, py::arg("table"), py::arg("rec"));
   m.def("cross_entropy_fwd", &ops::cross_entropy_fwd);
   m.def("cross_entropy_bwd", &ops::cross_entropy_bwd);
+  m.def("cross_entropy_mix_fwd", &ops::cross_entropy_mix_fwd);
+  m.def("cross_entropy_mix_bwd", &ops::cross_entropy_mix_bwd);
   // roctx tracing (rocprofv3 --marker-trace)
   m.def("trace_enabled", &trace::enabled);
   m.def("trace_set_enabled", &trace::set_enabled);
@@ -589,6 +591,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dropout_add_bf16", &ops::dropout_add_bf16, "y = res + m_row * m_elem * x, rounded to bf16 once",
         py::arg("x"), py::arg("res"), py::arg("snapshot"), py::arg("site_e"), py::arg("thr_e"), py::arg("site_r"),
         py::arg("thr_r"), py::arg("T"));
+  m.def("mix_draw", &ops::mix_draw, "mixup / cutmix records int32 [R, 8] = {lam, kind, y0, y1, x0, x1, lam0, 0}",
+        py::arg("snapshot"), py::arg("R"), py::arg("H"), py::arg("W"), py::arg("mixup_alpha"),
+        py::arg("cutmix_alpha"), py::arg("prob"), py::arg("switch_prob"));
+  m.def("mix_images", &ops::mix_images, "(x mixed with x.flip(0) as the records say, y.flip(0))", py::arg("x"),
+        py::arg("y"), py::arg("rec"));
   m.def("layernorm_fwd", &ops::layernorm_fwd);
   m.def("layernorm_bwd", &ops::layernorm_bwd);
   m.def("layernorm_fwd_q8", &ops::layernorm_fwd_q8, "layernorm forward with e4m3 outputs (q, q^T) at a delayed scale");

@@ -369,6 +369,158 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
   }
 }
 
+// Mixed targets (mixup / cutmix): row r carries the labels ya[r], yb[r] with the weights lam, 1 - lam, where
+// lam = lam_p[r * lam_stride] (stride 0: one value for the batch).  Row geometry, partials, last-arriver reduction
+// and workspace are ce_fwd_kernel's; every row is valid, so the count of a block is its number of rows.  With
+// lam == 1 (or 0) the loss and the gradient are bit for bit those of the index kernels on ya (or yb): the other
+// term is multiplied by an exact zero.  A label outside [0, C) reads no logit (its x[y] counts as 0).
+__device__ __forceinline__ float ce_mix_row_loss(float lam, float lse, float xa, float xb, float sx, int C,
+                                                 float eps) {
+  // No contraction here: ce_fwd_kernel's row loss compiles to two rounded products and an add (packed
+  // multiplies), and a fused form of the same expression would differ from it in the last bit.
+#pragma clang fp contract(off)
+  const float smooth = eps * (lse - sx / (float)C);
+  const float la = (1.f - eps) * (lse - xa) + smooth, lb = (1.f - eps) * (lse - xb) + smooth;
+  return lam * la + (1.f - lam) * lb;
+}
+
+template <bool kSmallC>
+__global__ __launch_bounds__(256) void ce_mix_fwd_kernel(const float* __restrict__ logits,
+                                                         const int64_t* __restrict__ ya,
+                                                         const int64_t* __restrict__ yb,
+                                                         const float* __restrict__ lam_p, int64_t lam_stride, int B,
+                                                         int C, float eps, int reduction,
+                                                         float* __restrict__ lse_out, float* __restrict__ loss,
+                                                         float* __restrict__ partials, unsigned* counter,
+                                                         int nparts) {
+  __shared__ float s_sum[256], s_cnt[256];
+  __shared__ int s_last;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float tsum = 0.f, tcnt = 0.f;
+  if (kSmallC) {
+    for (int r = blockIdx.x * 256 + tid; r < B; r += nparts * 256) {
+      const float* x = logits + (int64_t)r * C;
+      const int64_t a = ya[r], b = yb[r];
+      float mx = -INFINITY, sx = 0.f, xa = 0.f, xb = 0.f;
+      for (int c = 0; c < C; ++c) {
+        const float v = x[c];
+        mx = fmaxf(mx, v);
+        sx += v;
+        xa = (c == a) ? v : xa;
+        xb = (c == b) ? v : xb;
+      }
+      float se = 0.f;
+      for (int c = 0; c < C; ++c) se += __expf(x[c] - mx);
+      const float lse = mx + __logf(se);
+      const float l = ce_mix_row_loss(lam_p[r * lam_stride], lse, xa, xb, sx, C, eps);
+      lse_out[r] = lse;
+      if (reduction == 0) loss[r] = l;
+      tsum += l;
+      tcnt += 1.f;
+    }
+  } else {
+    for (int r = blockIdx.x * 4 + wave; r < B; r += nparts * 4) {
+      const float* x = logits + (int64_t)r * C;
+      float mx = -INFINITY;
+      for (int c = lane; c < C; c += 64) mx = fmaxf(mx, x[c]);
+      mx = wave_max(mx);
+      float se = 0.f, sx = 0.f;
+      for (int c = lane; c < C; c += 64) {
+        se += __expf(x[c] - mx);
+        sx += x[c];
+      }
+      se = wave_sum(se);
+      sx = wave_sum(sx);
+      const float lse = mx + __logf(se);
+      const int64_t a = ya[r], b = yb[r];
+      const float xa = (a >= 0 && a < C) ? x[a] : 0.f, xb = (b >= 0 && b < C) ? x[b] : 0.f;
+      const float l = ce_mix_row_loss(lam_p[r * lam_stride], lse, xa, xb, sx, C, eps);
+      if (lane == 0) {
+        lse_out[r] = lse;
+        if (reduction == 0) loss[r] = l;
+        tsum += l;
+        tcnt += 1.f;
+      }
+    }
+  }
+  if (reduction == 0) return;
+  s_sum[tid] = tsum;
+  s_cnt[tid] = tcnt;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {  // fixed-shape tree: deterministic
+    if (tid < off) {
+      s_sum[tid] += s_sum[tid + off];
+      s_cnt[tid] += s_cnt[tid + off];
+    }
+    __syncthreads();
+  }
+  if (nparts == 1) {
+    if (tid == 0) {
+      const float denom = reduction == 1 ? s_cnt[0] : 1.f;
+      partials[2 * nparts] = denom;
+      loss[0] = reduction == 1 ? s_sum[0] / denom : s_sum[0];
+    }
+    return;
+  }
+  if (tid == 0) {
+    partials[2 * blockIdx.x] = s_sum[0];
+    partials[2 * blockIdx.x + 1] = s_cnt[0];
+    // the hand-off of ce_fwd_kernel: publish the partial (agent-scope release), take a ticket, the last arriver reduces
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    unsigned t = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = (t == (unsigned)nparts - 1);
+    if (s_last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+  }
+  __syncthreads();
+  if (!s_last) return;
+  float a = 0.f, c = 0.f;
+  for (int i = tid; i < nparts; i += 256) {
+    a += __builtin_nontemporal_load(&partials[2 * i]);
+    c += __builtin_nontemporal_load(&partials[2 * i + 1]);
+  }
+  s_sum[tid] = a;
+  s_cnt[tid] = c;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off) {
+      s_sum[tid] += s_sum[tid + off];
+      s_cnt[tid] += s_cnt[tid + off];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const float denom = reduction == 1 ? s_cnt[0] : 1.f;
+    partials[2 * nparts] = denom;
+    loss[0] = reduction == 1 ? s_sum[0] / denom : s_sum[0];
+    __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+__global__ __launch_bounds__(256) void ce_mix_bwd_kernel(const float* __restrict__ logits,
+                                                         const int64_t* __restrict__ ya,
+                                                         const int64_t* __restrict__ yb,
+                                                         const float* __restrict__ lam_p, int64_t lam_stride,
+                                                         const float* __restrict__ lse,
+                                                         const float* __restrict__ grad_out,
+                                                         const float* __restrict__ denom, int B, int C, float eps,
+                                                         int reduction, float* __restrict__ dlogits) {
+  const int64_t n = (int64_t)B * C;
+  const float scale_all = reduction == 0 ? 1.f : grad_out[0] / denom[0];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int r = (int)(i / C), c = (int)(i % C);
+    const float lam = lam_p[r * lam_stride];
+    const float w = lam * (c == ya[r] ? 1.f : 0.f) + (1.f - lam) * (c == yb[r] ? 1.f : 0.f);
+    const float p = __expf(logits[i] - lse[r]);
+    const float q = (1.f - eps) * w + eps / (float)C;
+    dlogits[i] = (p - q) * (reduction == 0 ? grad_out[r] : scale_all);
+  }
+}
+
 // ---------------------------------------------------------------- synthetic data
 __device__ __forceinline__ uint32_t hash32(uint64_t x) {
   x ^= x >> 33;
@@ -462,6 +614,25 @@ void cross_entropy_bwd(const float* logits, const int64_t* labels, const float* 
   ce_bwd_kernel<<<grid_for(n, 256, 1024), 256, 0, s>>>(logits, labels, lse, grad_out, denom, B, C,
                                                        ignore_index, label_smoothing, reduction,
                                                        dlogits);
+}
+
+void cross_entropy_mix_fwd(const float* logits, const int64_t* ya, const int64_t* yb, const float* lam,
+                           int64_t lam_stride, int B, int C, float label_smoothing, int reduction, float* lse,
+                           float* loss, float* partials, unsigned* counter, int nparts, hipStream_t s) {
+  if (C <= kCeSmallC)
+    ce_mix_fwd_kernel<true><<<nparts, 256, 0, s>>>(logits, ya, yb, lam, lam_stride, B, C, label_smoothing,
+                                                   reduction, lse, loss, partials, counter, nparts);
+  else
+    ce_mix_fwd_kernel<false><<<nparts, 256, 0, s>>>(logits, ya, yb, lam, lam_stride, B, C, label_smoothing,
+                                                    reduction, lse, loss, partials, counter, nparts);
+}
+
+void cross_entropy_mix_bwd(const float* logits, const int64_t* ya, const int64_t* yb, const float* lam,
+                           int64_t lam_stride, const float* lse, const float* grad_out, const float* denom, int B,
+                           int C, float label_smoothing, int reduction, float* dlogits, hipStream_t s) {
+  const int64_t n = (int64_t)B * C;
+  ce_mix_bwd_kernel<<<grid_for(n, 256, 1024), 256, 0, s>>>(logits, ya, yb, lam, lam_stride, lse, grad_out, denom,
+                                                           B, C, label_smoothing, reduction, dlogits);
 }
 
 // Replay beacon: the last node of a captured step bumps a device counter and stores the new value

@@ -238,6 +238,14 @@ void cross_entropy_fwd(const float* logits, const int64_t* labels, int B, int C,
 void cross_entropy_bwd(const float* logits, const int64_t* labels, const float* lse,
                        const float* grad_out, const float* denom, int B, int C, int ignore_index,
                        float label_smoothing, int reduction, float* dlogits, hipStream_t s);
+// Mixed targets (mixup / cutmix): row r has labels ya[r], yb[r] weighted lam[r * lam_stride], 1 - lam (stride 0:
+// one lam for the batch).  Same geometry, workspace and reduction codes; every row counts (no ignore_index).
+void cross_entropy_mix_fwd(const float* logits, const int64_t* ya, const int64_t* yb, const float* lam,
+                           int64_t lam_stride, int B, int C, float label_smoothing, int reduction, float* lse,
+                           float* loss, float* partials, unsigned* counter, int nparts, hipStream_t s);
+void cross_entropy_mix_bwd(const float* logits, const int64_t* ya, const int64_t* yb, const float* lam,
+                           int64_t lam_stride, const float* lse, const float* grad_out, const float* denom, int B,
+                           int C, float label_smoothing, int reduction, float* dlogits, hipStream_t s);
 
 // ---------------------------------------------------------------- MNIST ConvNet
 // Activations are NHWC bf16 (a1 [B,13,13,32], a2 [B,10,10,64], a3 [B,16 windows,128]); weights are
@@ -632,6 +640,22 @@ void rng_tick(uint64_t* state, uint64_t* snapshot, hipStream_t s);
 //   res != nullptr:  y = m ? bf16(res + m * x) : res
 void dropout_bf16(const void* x, const void* res, const uint64_t* snapshot, uint32_t site_e, uint32_t thr_e,
                   uint32_t site_r, uint32_t thr_r, int64_t row_elems, int64_t n, void* y, hipStream_t s);
+
+// ---------------------------------------------------------------- mixup / cutmix (mixup.hip)
+// Records: int32 [R, 8] = {lam (fp32 bits), kind (0 not applied, 1 mixup, 2 cutmix), y0, y1, x0, x1, lam0 (fp32
+// bits), 0}; R = 1 (one decision per batch) or B (one per sample).  Drawn with Philox4x32-10, key = seed,
+// counter = (record, step lo, step hi, round), from the (seed, step) snapshot of rng_tick.
+struct MixDrawArgs {
+  float mixup_alpha, cutmix_alpha, prob, switch_prob;
+  int H, W, R;
+};
+void mix_draw(const uint64_t* snapshot, const MixDrawArgs& a, int32_t* rec, hipStream_t s);
+// out[b] = x[b] mixed with x[B - 1 - b] as record b (elem) or record 0 says, y_b[b] = y[B - 1 - b].  A sample is
+// sample_elems = outer * H * W * inner elements (inner = 1: NCHW, inner = C: channels-last) of bf16 or fp32.
+// vec: 16-byte accesses (sample bytes % 16 == 0 and 16-byte aligned x / out), otherwise one element per thread.
+// B * sample_elems < 2^31.  out must not alias x.
+void mix_images(const void* x, bool x_bf16, const int64_t* y, const int32_t* rec, bool elem, int64_t B,
+                int64_t sample_elems, int H, int W, int inner, bool vec, void* out, int64_t* y_b, hipStream_t s);
 
 // ---------------------------------------------------------------- data
 // Gather B samples of a uint8 (N, H, W, C) dataset by index, random-crop (zero pad) + h-flip, then

@@ -60,6 +60,13 @@ at::Tensor dropout_bf16(const at::Tensor& x, const c10::optional<at::Tensor>& sn
 at::Tensor dropout_add_bf16(const at::Tensor& x, const at::Tensor& res, const c10::optional<at::Tensor>& snapshot,
                             int64_t site_e, int64_t thr_e, int64_t site_r, int64_t thr_r, int64_t T);
 
+// Mixup / CutMix (mixup_ops.cpp).  mix_draw: int32 [R, 8] records {lam, kind, y0, y1, x0, x1, lam0, 0} drawn from an
+// rng_tick snapshot, R = 1 (per batch) or B (per sample).  mix_images: (x mixed with x.flip(0), y.flip(0)) for
+// x [B, C, H, W] bf16 / fp32, NCHW or channels-last; a fresh tensor, x is not written.
+at::Tensor mix_draw(const at::Tensor& snapshot, int64_t R, int64_t H, int64_t W, double mixup_alpha,
+                    double cutmix_alpha, double prob, double switch_prob);
+std::tuple<at::Tensor, at::Tensor> mix_images(const at::Tensor& x, const at::Tensor& y, const at::Tensor& rec);
+
 std::tuple<at::Tensor, at::Tensor> layernorm_fwd(const at::Tensor& x, const at::Tensor& w, const at::Tensor& b,
                                                  double eps);
 // LayerNorm forward writing e4m3 (delayed scaling, hist = [amax, per-64-row-block maxima]): [stats, q, qt, scale]

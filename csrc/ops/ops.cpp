@@ -502,6 +502,73 @@ at::Tensor cross_entropy_bwd(const at::Tensor& logits, const at::Tensor& labels,
   return d;
 }
 
+namespace {
+// lam: fp32 [1] (one value for the batch) or [B] with any stride, e.g. word 0 of the mixup records
+int64_t check_mix_targets(const at::Tensor& logits, const at::Tensor& ya, const at::Tensor& yb, const at::Tensor& lam) {
+  check_cuda(logits, "cross_entropy_mix logits");
+  check_cuda(ya, "cross_entropy_mix y_a");
+  check_cuda(yb, "cross_entropy_mix y_b");
+  check_dtype(logits, at::kFloat, "cross_entropy_mix logits");
+  check_dtype(ya, at::kLong, "cross_entropy_mix y_a");
+  check_dtype(yb, at::kLong, "cross_entropy_mix y_b");
+  RINGDP_CHECK(logits.dim() == 2 && ya.dim() == 1 && yb.dim() == 1 && ya.size(0) == logits.size(0) &&
+                   yb.size(0) == logits.size(0) && logits.size(0) > 0 && logits.size(1) > 0,
+               "cross_entropy_mix: expected logits [B, C] and labels y_a, y_b [B]");
+  RINGDP_CHECK(lam.defined() && lam.is_cuda() && lam.scalar_type() == at::kFloat && lam.dim() == 1 &&
+                   (lam.size(0) == 1 || lam.size(0) == logits.size(0)),
+               "cross_entropy_mix lam: expected a GPU fp32 tensor of shape [1] or [B]");
+  RINGDP_CHECK(ya.get_device() == logits.get_device() && yb.get_device() == logits.get_device() &&
+                   lam.get_device() == logits.get_device(),
+               "cross_entropy_mix: tensors on different devices");
+  return lam.size(0) == 1 ? 0 : lam.stride(0);
+}
+}  // namespace
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> cross_entropy_mix_fwd(const at::Tensor& logits, const at::Tensor& ya,
+                                                                     const at::Tensor& yb, const at::Tensor& lam,
+                                                                     double smoothing, int64_t reduction) {
+  const int64_t lam_stride = check_mix_targets(logits, ya, yb, lam);
+  RINGDP_CHECK(reduction >= 0 && reduction <= 2, "cross_entropy_mix: bad reduction ", reduction);
+  const int B = static_cast<int>(logits.size(0)), C = static_cast<int>(logits.size(1));
+  const int nparts = kern::cross_entropy_parts(B, C);
+  c10::DeviceGuard guard(logits.device());
+  auto fo = logits.options();
+  at::Tensor lse = at::empty({B}, fo);
+  at::Tensor loss = reduction == 0 ? at::empty({B}, fo) : at::empty({}, fo);
+  at::Tensor ws = at::empty({2 * nparts + 4}, fo);  // as cross_entropy_fwd: [2*nparts partials][denom][3 pad]
+  kern::cross_entropy_mix_fwd(logits.data_ptr<float>(), ya.data_ptr<int64_t>(), yb.data_ptr<int64_t>(),
+                              lam.data_ptr<float>(), lam_stride, B, C, static_cast<float>(smoothing),
+                              static_cast<int>(reduction), lse.data_ptr<float>(), loss.data_ptr<float>(),
+                              ws.data_ptr<float>(), next_counter(logits), nparts, cur_stream(logits));
+  return {loss, lse, ws};
+}
+
+at::Tensor cross_entropy_mix_bwd(const at::Tensor& logits, const at::Tensor& ya, const at::Tensor& yb,
+                                 const at::Tensor& lam, const at::Tensor& lse, const at::Tensor& ws,
+                                 const at::Tensor& grad_out, double smoothing, int64_t reduction) {
+  const int64_t lam_stride = check_mix_targets(logits, ya, yb, lam);
+  check_cuda(grad_out, "cross_entropy_mix grad_out");
+  check_cuda(lse, "cross_entropy_mix lse");
+  check_cuda(ws, "cross_entropy_mix workspace");
+  check_dtype(lse, at::kFloat, "cross_entropy_mix lse");
+  check_dtype(ws, at::kFloat, "cross_entropy_mix workspace");
+  const int B = static_cast<int>(logits.size(0)), C = static_cast<int>(logits.size(1));
+  const int nparts = kern::cross_entropy_parts(B, C);
+  RINGDP_CHECK(reduction >= 0 && reduction <= 2, "cross_entropy_mix: bad reduction ", reduction);
+  RINGDP_CHECK(lse.numel() == B && ws.numel() == 2 * nparts + 4,
+               "cross_entropy_mix: lse / workspace are not this forward's");
+  at::Tensor g = grad_out.to(at::kFloat).contiguous();
+  RINGDP_CHECK(g.numel() == (reduction == 0 ? B : 1), "cross_entropy_mix grad_out: expected ",
+               reduction == 0 ? B : 1, " values, got ", g.numel());
+  c10::DeviceGuard guard(logits.device());
+  at::Tensor d = at::empty_like(logits);
+  kern::cross_entropy_mix_bwd(logits.data_ptr<float>(), ya.data_ptr<int64_t>(), yb.data_ptr<int64_t>(),
+                              lam.data_ptr<float>(), lam_stride, lse.data_ptr<float>(), g.data_ptr<float>(),
+                              ws.data_ptr<float>() + 2 * nparts, B, C, static_cast<float>(smoothing),
+                              static_cast<int>(reduction), d.data_ptr<float>(), cur_stream(logits));
+  return d;
+}
+
 // ------------------------------------------------------------------ ConvNet
 namespace {
 void check_input(const at::Tensor& x, int64_t& B, bool& u8) {

@@ -96,6 +96,14 @@ at::Tensor cross_entropy_bwd(const at::Tensor& logits, const at::Tensor& labels,
                              const at::Tensor& lse, const at::Tensor& ws,
                              const at::Tensor& grad_out, int64_t ignore_index,
                              double label_smoothing, int64_t reduction);
+// Mixed targets: labels y_a, y_b [B] weighted lam, 1 - lam; lam is fp32 [1] or [B] with any stride (word 0 of the
+// mixup records).  Returns (loss, lse, workspace) as cross_entropy_fwd.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> cross_entropy_mix_fwd(const at::Tensor& logits, const at::Tensor& ya,
+                                                                     const at::Tensor& yb, const at::Tensor& lam,
+                                                                     double label_smoothing, int64_t reduction);
+at::Tensor cross_entropy_mix_bwd(const at::Tensor& logits, const at::Tensor& ya, const at::Tensor& yb,
+                                 const at::Tensor& lam, const at::Tensor& lse, const at::Tensor& ws,
+                                 const at::Tensor& grad_out, double label_smoothing, int64_t reduction);
 
 // MNIST ConvNet blocks (see csrc/kernels/convnet_fwd.hip for the F1/F2/F3 split).
 at::Tensor cn_pack_weights(const at::Tensor& w1, const at::Tensor& w2, const at::Tensor& w3,

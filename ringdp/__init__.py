@@ -7,7 +7,7 @@ over xGMI:
 * ``ringdp.distributed``  - init_process_group / collectives (C++ TCP store, RCCL and host-ring
                             process groups, watchdog, debug fingerprints, fault injection)
 * ``ringdp.parallel``     - DistributedDataParallel on a C++ bucketed reducer
-* ``ringdp.data``         - DistributedSampler (+ on-device variants), datasets, transforms
+* ``ringdp.data``         - DistributedSampler (+ on-device variants), datasets, transforms, Mixup / CutMix
 * ``ringdp.multiprocessing.spawn`` / ``python -m ringdp.run`` / ``python -m ringdp.launch``
 * ``ringdp.models``       - ConvNet (MNIST) on fused MFMA kernels; ResNet / ViT families
 * ``ringdp.nn`` / ``ringdp.optim`` - cross entropy, dropout, fused SGD / AdamW

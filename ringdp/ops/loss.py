@@ -4,6 +4,7 @@ from __future__ import annotations
 import torch
 
 from .._native import C
+from .mixup import MixedTarget, mixed_cross_entropy
 
 _RED = {"none": 0, "mean": 1, "sum": 2}
 
@@ -25,8 +26,14 @@ class _CrossEntropy(torch.autograd.Function):
         return d, None, None, None, None
 
 
-def cross_entropy(logits: torch.Tensor, target: torch.Tensor, ignore_index: int = -100,
+def cross_entropy(logits: torch.Tensor, target, ignore_index: int = -100,
                   label_smoothing: float = 0.0, reduction: str = "mean") -> torch.Tensor:
+    """``target``: class indices, or a ``MixedTarget`` (mixup / cutmix, ``ringdp.ops.mixup``) - every row counts
+    then, so ``ignore_index`` has to stay at its default."""
+    if isinstance(target, MixedTarget):
+        if ignore_index != -100:
+            raise ValueError("cross_entropy: ignore_index is not supported with a MixedTarget")
+        return mixed_cross_entropy(logits, target, label_smoothing, reduction)
     if logits.is_cuda and logits.dim() == 2 and target.dim() == 1:
         from .convnet import head_cross_entropy
         from .convnet_fp32 import head_cross_entropy_fp32
