@@ -529,7 +529,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_property_readonly("nchunks", &ops::AdamTable::nchunks)
       .def_readonly("chunk_starts", &ops::AdamTable::chunk_starts)
       .def_readonly("all_aligned", &ops::AdamTable::all_aligned)
-      .def_readonly("full", &ops::AdamTable::full);
+      .def_readonly("full", &ops::AdamTable::full)
+      .def_readonly("pair", &ops::AdamTable::pair);
   m.def("adam_table_build", &ops::adam_table_build, py::arg("params"), py::arg("grads"), py::arg("exp_avgs"),
         py::arg("exp_avg_sqs"), py::arg("group_sizes"));
   m.def("grad_sumsq_run", &ops::grad_sumsq_run, py::arg("table"), py::arg("partials"));
@@ -540,6 +541,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adam_update_flat", &ops::adam_update_flat, py::arg("param"), py::arg("grad"), py::arg("exp_avg"),
         py::arg("exp_avg_sq"), py::arg("rec"), py::arg("rec_group"), py::arg("hyper"));
   m.def("grad_scale_run", &ops::grad_scale_run, py::arg("table"), py::arg("rec"));
+  py::class_<ops::LrSchedSpec>(m, "LrSchedSpec")
+      .def(py::init<>())
+      .def_readwrite("kind", &ops::LrSchedSpec::kind)
+      .def_readwrite("period", &ops::LrSchedSpec::period)
+      .def_readwrite("warmup_steps", &ops::LrSchedSpec::warmup_steps)
+      .def_readwrite("total_steps", &ops::LrSchedSpec::total_steps)
+      .def_readwrite("warmup_start_factor", &ops::LrSchedSpec::warmup_start_factor)
+      .def_readwrite("min_factor", &ops::LrSchedSpec::min_factor)
+      .def_readwrite("power", &ops::LrSchedSpec::power)
+      .def_readwrite("gamma", &ops::LrSchedSpec::gamma)
+      .def_readwrite("milestones", &ops::LrSchedSpec::milestones);
+  m.def("lr_sched_run", &ops::lr_sched_run, "counter [+= 1]; lr_tensors[g] = base_lrs[g] * factor(counter)",
+        py::arg("counter"), py::arg("spec"), py::arg("base_lrs"), py::arg("lr_tensors"), py::arg("advance"));
+  m.def("ema_tick_run", &ops::ema_tick_run, "num_updates += 1; w = 1 - decay_n", py::arg("num_updates"),
+        py::arg("w"), py::arg("decay"), py::arg("warmup"));
+  m.def("ema_update_run", &ops::ema_update_run, "shadow = fma(w, source - shadow, shadow) over a pair table",
+        py::arg("table"), py::arg("w"));
+  m.def("ema_update_flat", &ops::ema_update_flat, py::arg("shadow"), py::arg("source"), py::arg("w"));
   m.def("cross_entropy_fwd", &ops::cross_entropy_fwd);
   m.def("cross_entropy_bwd", &ops::cross_entropy_bwd);
   m.def("cross_entropy_mix_fwd", &ops::cross_entropy_mix_fwd);

@@ -46,7 +46,7 @@ void sgd_multi(const SgdTensor* table, const int64_t* chunks, int64_t nchunks, i
 // ---------------------------------------------------------------- Adam / AdamW + global-norm clipping (optim.hip)
 // No atomics, arrival counters or fences: grad_sumsq -> adam_prepare -> adam_update are ordered by kernel
 // boundaries on one stream, so a step is deterministic and hipGraph-capturable.
-struct AdamTensor {  // p / m / v may be null in a table that only the gradient kernels walk
+struct AdamTensor {  // p / m / v may be null in a table that only the gradient kernels walk; m / v in the EMA's
   float* p;
   float* g;
   float* m;
@@ -91,6 +91,40 @@ void adam_update_flat(float* p, const float* g, float* m, float* v, int64_t n, c
 // g *= clip_coef (rec[1]) in place over the table.
 void grad_scale_multi(const AdamTensor* table, const int64_t* chunks, int64_t nchunks, const float* rec,
                       hipStream_t s);
+
+// ---------------------------------------------------------------- LR schedules + model EMA (sched_ema.hip)
+// A scalar derived from a device step counter, then one stream pass: no atomics, no fences, ordered by kernel
+// boundaries like the optimizer, so both are deterministic and hipGraph-capturable.
+constexpr int kSchedMaxMilestones = 8;
+enum SchedKind : int { kSchedConstant = 0, kSchedCosine = 1, kSchedPoly = 2, kSchedMultiStep = 3 };
+struct LrSchedSpec {  // the factor f(t) of ringdp/optim/lr_scheduler.py
+  int kind;
+  int nmilestones;
+  int64_t period, warmup_steps, total_steps;
+  double warmup_start_factor, min_factor, power, gamma;
+  int64_t milestones[kSchedMaxMilestones];
+};
+struct LrSchedGroup {
+  double base_lr;
+  float* lr_ptr;  // the group's 0-dim fp32 lr the optimizer kernels read
+};
+struct LrSchedArgs {
+  int64_t* counter;  // device step counter t
+  int ngroups;
+  int advance;  // 1: t += 1 before evaluating; 0: re-evaluate at t
+  LrSchedSpec spec;
+  LrSchedGroup group[kAdamMaxGroups];
+};
+// One workgroup: lr_ptr[g] = (float)(base_lr[g] * f(t [+ 1])), then the counter is stored.
+void lr_sched(const LrSchedArgs& a, hipStream_t s);
+// One thread: n = ++*num_updates; *w = (float)(1 - decay_n), decay_n = decay or, with warmup,
+// min(decay, (1 + n) / (10 + n)) in fp64.
+void ema_tick(int64_t* num_updates, float* w, double decay, bool warmup, hipStream_t s);
+// e = fmaf(w, p - e, e) with e = table[].p (shadow) and p = table[].g (source); m / v are not read.
+void ema_update_multi(const AdamTensor* table, const int64_t* chunks, int64_t nchunks, const float* w,
+                      bool all_aligned, hipStream_t s);
+// Flat range, both buffers 16-byte aligned.
+void ema_update_flat(float* e, const float* p, int64_t n, const float* w, hipStream_t s);
 
 // Deterministic split-K reduction: out[i] = sum_s slabs[s * n + i] (fixed order).
 void splitk_reduce(const float* slabs, int nslices, int64_t n, float* out, hipStream_t s);

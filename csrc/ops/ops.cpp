@@ -297,11 +297,14 @@ AdamTable adam_table_build(std::vector<at::Tensor> params, std::vector<at::Tenso
                            std::vector<at::Tensor> exp_avgs, std::vector<at::Tensor> exp_avg_sqs,
                            std::vector<int64_t> group_sizes) {
   const size_t n = grads.size();
-  const bool full = !params.empty();
+  const bool pair = !params.empty() && exp_avgs.empty() && exp_avg_sqs.empty();
+  const bool full = !params.empty() && !pair;
   RINGDP_CHECK(n > 0, "adam_table_build: no tensors");
   if (full)
     RINGDP_CHECK(params.size() == n && exp_avgs.size() == n && exp_avg_sqs.size() == n,
                  "adam_table_build: need one grad, exp_avg and exp_avg_sq per param");
+  else if (pair)
+    RINGDP_CHECK(params.size() == n, "adam_table_build: need one grad per param");
   else
     RINGDP_CHECK(exp_avgs.empty() && exp_avg_sqs.empty(), "adam_table_build: state tensors without params");
   int64_t covered = 0;
@@ -323,10 +326,10 @@ AdamTable adam_table_build(std::vector<at::Tensor> params, std::vector<at::Tenso
       RINGDP_CHECK(grads[i].get_device() == grads[0].get_device(), "adam_table_build: tensors on several devices");
       kern::AdamTensor e{nullptr, grads[i].data_ptr<float>(), nullptr, nullptr, grads[i].numel()};
       al = al && aligned16(grads[i]);
-      if (full) {
-        const at::Tensor* ts[3] = {&params[i], &exp_avgs[i], &exp_avg_sqs[i]};
+      if (full || pair) {
+        const at::Tensor* ts[3] = {&params[i], full ? &exp_avgs[i] : nullptr, full ? &exp_avg_sqs[i] : nullptr};
         const char* names[3] = {"adam param", "adam exp_avg", "adam exp_avg_sq"};
-        for (int k = 0; k < 3; ++k) {
+        for (int k = 0; k < (full ? 3 : 1); ++k) {
           check_cuda(*ts[k], names[k]);
           check_dtype(*ts[k], at::kFloat, names[k]);
           RINGDP_CHECK(ts[k]->numel() == e.n, names[k], ": numel mismatch with the grad at ", i);
@@ -334,8 +337,10 @@ AdamTable adam_table_build(std::vector<at::Tensor> params, std::vector<at::Tenso
           al = al && aligned16(*ts[k]);
         }
         e.p = params[i].data_ptr<float>();
-        e.m = exp_avgs[i].data_ptr<float>();
-        e.v = exp_avg_sqs[i].data_ptr<float>();
+        if (full) {
+          e.m = exp_avgs[i].data_ptr<float>();
+          e.v = exp_avg_sqs[i].data_ptr<float>();
+        }
       }
       table[i] = e;
       for (int64_t s = 0; s < e.n; s += kern::kAdamChunk) {
@@ -357,6 +362,7 @@ AdamTable adam_table_build(std::vector<at::Tensor> params, std::vector<at::Tenso
   t.chunk_starts = starts;
   t.all_aligned = aligned;
   t.full = full;
+  t.pair = pair;
   return t;
 }
 

@@ -58,7 +58,7 @@ struct AdamHyper {
 };
 // Device table over fp32 tensors, listed group after group (group_sizes[i] tensors each): {p, g, m, v, n} entries
 // followed by the {tensor, start} chunk list.  params / exp_avgs / exp_avg_sqs may all be empty (a table for the
-// gradient kernels only).  The upload is synchronous, so the table can be cached and the kernels that walk it
+// gradient kernels only), or only the two moment lists (m / v null: a table of {p, g} pairs).  The upload is synchronous, so the table can be cached and the kernels that walk it
 // captured, same contract as sgd_multi_build.  Everything the launches rely on was checked when it was built.
 struct AdamTable {
   at::Tensor dev;
@@ -66,6 +66,7 @@ struct AdamTable {
   std::vector<int64_t> chunk_starts;  // groups + 1 entries
   std::vector<bool> all_aligned;      // per group: every base 16-byte aligned
   bool full = false;                  // holds p / m / v, not only gradients
+  bool pair = false;                  // holds p and g only (exp_avgs / exp_avg_sqs empty): the model EMA's table
   int64_t nchunks() const { return chunk_starts.empty() ? 0 : chunk_starts.back(); }
 };
 AdamTable adam_table_build(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
@@ -85,6 +86,28 @@ void adam_update_flat(at::Tensor param, const at::Tensor& grad, at::Tensor exp_a
                       const at::Tensor& rec, int64_t rec_group, const AdamHyper& h);
 // g *= rec[1] in place over the whole table.
 void grad_scale_run(const AdamTable& table, const at::Tensor& rec);
+
+// ---- Device-side LR schedules and the model EMA (sched_ema_ops.cpp, csrc/kernels/sched_ema.hip).
+struct LrSchedSpec {
+  int64_t kind = 0;  // kern::SchedKind
+  int64_t period = 1;
+  int64_t warmup_steps = 0;
+  int64_t total_steps = 1;
+  double warmup_start_factor = 0.0;
+  double min_factor = 0.0;
+  double power = 1.0;
+  double gamma = 0.1;
+  std::vector<int64_t> milestones;
+};
+// counter (int64, one element) [+= 1 when advance]; lr_tensors[g] = (float)(base_lrs[g] * f(counter)).  One launch.
+void lr_sched_run(at::Tensor counter, const LrSchedSpec& spec, const std::vector<double>& base_lrs,
+                  std::vector<at::Tensor> lr_tensors, bool advance);
+// num_updates (int64, one element) += 1; w (fp32, one element) = 1 - decay_n.
+void ema_tick_run(at::Tensor num_updates, at::Tensor w, double decay, bool warmup);
+// shadow = fmaf(w, source - shadow, shadow) over a table built with params = shadows, grads = sources and no
+// moments (adam_table_build), or over one flat range.
+void ema_update_run(const AdamTable& table, const at::Tensor& w);
+void ema_update_flat(at::Tensor shadow, const at::Tensor& source, const at::Tensor& w);
 
 // Cross entropy: returns (loss, lse, workspace); workspace holds the denominator for backward.
 std::tuple<at::Tensor, at::Tensor, at::Tensor> cross_entropy_fwd(const at::Tensor& logits,

@@ -10,7 +10,8 @@ over xGMI:
 * ``ringdp.data``         - DistributedSampler (+ on-device variants), datasets, transforms, Mixup / CutMix
 * ``ringdp.multiprocessing.spawn`` / ``python -m ringdp.run`` / ``python -m ringdp.launch``
 * ``ringdp.models``       - ConvNet (MNIST) on fused MFMA kernels; ResNet / ViT families
-* ``ringdp.nn`` / ``ringdp.optim`` - cross entropy, dropout, fused SGD / AdamW
+* ``ringdp.nn`` / ``ringdp.optim`` - cross entropy, dropout, fused SGD / AdamW, device-side LR schedules
+* ``ringdp.utils``        - hipGraph step capture, checkpointing, ModelEma (fused EMA of the weights)
 * ``ringdp.random``       - device-resident generator state of the dropout masks (hipGraph-safe)
 """
 from . import distributed  # noqa: F401

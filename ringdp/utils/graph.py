@@ -11,6 +11,8 @@ them), DDP bucket rebuild must have happened (warmup >= 2 steps), and the optimi
 its graph-safe path (ringdp.optim.SGD flat path: no allocations, lr may be a device tensor; ringdp.optim.AdamW /
 Adam, flat or multi-tensor once warm-up built their table: the step count, the bias corrections, the clip
 coefficient of max_grad_norm and a tensor lr all live on the device, so every replay advances them).
+ringdp.optim.lr_scheduler's ``step()`` and ``ModelEma.update()`` may be part of the step: their counters live on the
+device too, and the warm-up steps build the EMA's pointer table before the capture.
 """
 from __future__ import annotations
 
