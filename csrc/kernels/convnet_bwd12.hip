@@ -13,6 +13,12 @@ __device__ __forceinline__ bf16x8 ones_column_frag(int lane) {
   return bf16x8{one, one, one, one, one, one, one, one};
 }
 
+// a * b per 16-bit half (v_pk_mul_lo_u16)
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t pk_mul_u16(uint32_t a, uint32_t b) {
+  return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, a) * __builtin_bit_cast(u16x2, b));
+}
+
 // ================================================================== F2 backward
 // conv2's ReLU and pool2 are undone by F3's backward, so dz2 is the conv output gradient directly:
 //   dgrad: da1 = full-corr(dz2 image, flipped W2)  [13x13x32]
@@ -541,10 +547,11 @@ __global__ __launch_bounds__(512) void conv12_bwd_kernel(const void* __restrict_
 //   dgrad: waves 0-3 run conv2's data gradient of image s (both 16-channel n-tiles per wave, so every
 //     A-fragment read feeds 2 MFMAs: half the LDS reads of conv12_dgrad_role) into da1 O[s&1]; beside them
 //     waves 4-7 stage image s+1 (dz2 -> P, input copies, pool1 codes; registers loaded two steps ahead).
-//     conv1's weight gradient of image s-1 (from O[(s-1)&1]) is shared by all 8 waves: 16 of its 26 k-steps
-//     on waves 4-7, 10 on waves 0-3 after their conv2 phase (profiles/r07/c12_bwd/README.md: the MFMA waves
-//     had waited 2000 of 5400 cycles per image at the barrier).  One barrier per image.  The input copies
-//     and codes of image s-1 are still read while image s+1 is staged: three of those.
+//     conv1's weight gradient of image s-1 (from O[(s-1)&1]) runs on the sparse MFMA, 13 steps of one window
+//     row each: 12 on waves 4-7 and 1 on wave 3 after its conv2 phase, none on waves 0-2, which end their
+//     conv2 phase when the helper waves end their steps (profiles/r13/c1_wgrad_sparse/README.md).  One barrier
+//     per image.  The input copies and codes of image s-1 are still read while image s+1 is staged: three of
+//     those.
 //   wgrad: conv2's weight gradient, 8 waves each 2 co tiles x 4-5 n-tiles (14 tr16 reads per 10 MFMAs per
 //     k-step instead of 20 per 9), image i+2 staged from registers while image i's MFMAs run (waves 0-3
 //     before their k-steps, waves 4-7 after theirs).
@@ -597,17 +604,27 @@ __device__ __forceinline__ void conv12_dgrad8_role(char* smem, const void* __res
     reinterpret_cast<bf16x8*>(smem)[c] = zero_bf16x8();
   __syncthreads();
   if ((ablate & 8) && wave >= 4) __builtin_amdgcn_s_setprio(1);
-  // ---- conv1's weight gradient of one image, 26 k-steps (window row py = ks >> 1, row half dy = ks & 1) shared
-  // by all 8 waves: the MFMA waves end their conv2 phase well before the helper waves end theirs, so MFMA
-  // waves 0-2 take C12_KM k-steps each and wave 3 (2 m-tiles) C12_KM3; the helper waves share the first C12_KH
-  // (vw, vw + 4, ..).  Every wave sums its own k-steps over all images; the 8 partial sums are combined at the
-  // end in a fixed order.  All LDS addresses are 32-bit byte offsets from smem: a per-lane part formed once and
-  // scalar per-image and per-k-step parts.  (Formed from pointers they compiled to 64-bit multiply-adds whose
-  // undefined high halves shared registers with the global loads in flight, and the loop waited for those.)
-  constexpr int C12_KM = 2, C12_KM3 = 4, C12_KH = 26 - 3 * C12_KM - C12_KM3;
-  static_assert(C12_KH >= 4 && C12_KM >= 0 && C12_KM3 >= 0, "conv1 k-step partition");
-  const int k0 = wave < 4 ? C12_KH + wave * C12_KM : wave - 4, kst = wave < 4 ? 1 : 4;
-  const int kcnt = wave < 3 ? C12_KM : wave == 3 ? C12_KM3 : (C12_KH - (wave - 4) + 3) / 4;
+  // ---- conv1's weight gradient of one image on the sparse MFMA.  pool1 is 2x2 / stride 2, so of the four dC
+  // positions of a window at most one is live, and an aligned group of four dense columns (k = oh * 32 + ow) is two
+  // neighbouring windows in one row half: the 2-of-4 pattern of v_smfmac_f32_16x16x64_bf16 (layout: smfmac16x16x64).
+  // One sparse step covers window row py, i.e. the dense k-steps 2py (dy = 0) and 2py + 1 (dy = 1): 13 steps of
+  // 4 MFMAs per image.  Lane (i16 = channel, G = lane >> 4) holds row half dy = G >> 1, windows 8 (G & 1) .. + 7:
+  //   values: two ds_read_b64_tr_b16 of the da1 image deliver the eight windows in slot order, two per dword.  da1
+  //     is not masked, so a slot keeps its value only if the window's one-hot code has a bit in row dy (a
+  //     ReLU-dead window has none, windows 13..15 have zero code bytes): one 0 / 1 factor per 16-bit half, so a
+  //     dead slot is +0.0 whatever the da1 bits were.
+  //   index: slot e stands for column 2 (e & 1) + dx of its group, dx = the upper of the code's two row-dy bits.
+  //   B: the dense fragments of k-steps 2py and 2py + 1 back to back (tap column 25 all ones -> db1).
+  // The MFMA waves 0-2 end their conv2 phase last and take none; wave 3 (2 m-tiles) takes C12_S3 steps and the
+  // helper waves share the first 13 - C12_S3 (vw, vw + 4, ..).  Every wave sums its own steps over all images
+  // (none: zeros); the 8 partial sums are combined at the end in a fixed order.  All LDS addresses are 32-bit
+  // byte offsets from smem: a per-lane part formed once and scalar per-image and per-step parts.  (Formed from
+  // pointers they compiled to 64-bit multiply-adds whose undefined high halves shared registers with the global
+  // loads in flight, and the loop waited for those.)
+  constexpr int C12_S3 = 1, C12_SH = 13 - C12_S3;
+  static_assert(C12_SH >= 4 && C12_S3 >= 0, "conv1 step partition");
+  const int k0 = wave < 4 ? C12_SH : wave - 4, kst = wave < 4 ? 1 : 4;
+  const int kcnt = wave < 3 ? 0 : wave == 3 ? C12_S3 : (C12_SH - (wave - 4) + 3) / 4;
   const int i16 = lane & 15, g = lane >> 4, q = i16 >> 2, p = i16 & 3;
   const int t1 = 16 + i16;
   const int xoff0 = (i16 % 5) * C1W_CS + (i16 / 5) * C1W_RS + 8 * g;
@@ -616,60 +633,73 @@ __device__ __forceinline__ void conv12_dgrad8_role(char* smem, const void* __res
   f32x4 acc1[2][2];
 #pragma unroll
   for (int m = 0; m < 2; ++m) acc1[m][0] = acc1[m][1] = zero_f32x4();
-  const int o_lane = ((4 * g + q) * C2_ORS + 4 * p) * 2;
-  const int c_lane = (i16 >> 1) * 16 + 4 * g, csh_lane = 4 * (i16 & 1);
+  const int o_lane = ((8 * (g & 1) + q) * C2_ORS + 4 * p) * 2;
+  const int c_lane = (i16 >> 1) * 16 + 8 * (g & 1);
+  const uint32_t csh = 4 * (i16 & 1) + 2 * (g >> 1);  // this lane's two code bits: channel parity, row half
   struct C1F {
-    uint2 d[2];
-    uint32_t cu[2];
-    bf16x8 b0, b1;
+    uint2 d[2][2];  // [m-tile][windows 8 (G & 1) .., + 4]
+    uint2 cu[2];
+    bf16x8 b0[2], b1[2];  // [row half]
   };
   // oimg / ximg / cimg: byte offsets of the image's da1, input copies and codes
-  auto c1_read = [&](int ks, int oimg, int ximg, int cimg, C1F& f) {
-    const int py = ks >> 1;
+  auto c1_read = [&](int py, int oimg, int ximg, int cimg, C1F& f) {
     int oa = oimg + py * (13 * C2_ORS * 2) + o_lane, ca = cimg + py * 256 + c_lane;
-    int x0 = ximg + ks * (C1W_RS * 2) + xoff0 * 2, x1 = ximg + ks * (C1W_RS * 2) + xoff1 * 2;
-    asm("" : "+v"(oa), "+v"(ca), "+v"(x0), "+v"(x1));  // one VGPR address each; m is an immediate offset
+    int x0 = ximg + py * (2 * C1W_RS * 2) + xoff0 * 2, x1 = ximg + py * (2 * C1W_RS * 2) + xoff1 * 2;
+    asm("" : "+v"(oa), "+v"(ca), "+v"(x0), "+v"(x1));  // one VGPR address each; the rest are immediate offsets
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
-      f.d[m] = __builtin_bit_cast(uint2, lds_read_tr16(reinterpret_cast<const bf16*>(smem + oa) + m * 16));
-      f.cu[m] = *reinterpret_cast<const uint32_t*>(smem + ca + m * 128);
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        f.d[m][h] = __builtin_bit_cast(
+            uint2, lds_read_tr16(reinterpret_cast<const bf16*>(smem + oa) + h * 4 * C2_ORS + m * 16));
+      f.cu[m] = *reinterpret_cast<const uint2*>(smem + ca + m * 128);
     }
-    f.b0 = *reinterpret_cast<const bf16x8*>(smem + x0);
-    f.b1 = *reinterpret_cast<const bf16x8*>(smem + x1);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      f.b0[h] = *reinterpret_cast<const bf16x8*>(smem + x0 + h * C1W_RS * 2);
+      f.b1[h] = *reinterpret_cast<const bf16x8*>(smem + x1 + h * C1W_RS * 2);
+    }
   };
-  auto c1_mma = [&](int ks, const C1F& f) {
+  auto c1_mma = [&](const C1F& f) {
     bf16x8 A[2];
-    const int csh = csh_lane + 2 * (ks & 1);
+    int ix[2];
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
-      const uint2 d = f.d[m];
-      const uint32_t cu = f.cu[m];
-      uint32_t pr[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const uint32_t dv = e & 1 ? (e < 2 ? d.x : d.y) >> 16 : (e < 2 ? d.x : d.y) & 0xffffu;
-        const uint32_t sel = __builtin_amdgcn_ubfe(cu, 8 * e + csh, 2);
-        pr[e] = dv * ((sel * 0x8001u) & 0x10001u);
-      }
-      A[m] = __builtin_bit_cast(bf16x8, make_uint4(pr[0], pr[1], pr[2], pr[3]));
+      const uint32_t ux = f.cu[m].x >> csh, uy = f.cu[m].y >> csh;  // byte e, bits 0-1: 1 -> dx 0, 2 -> dx 1, 0 -> dead
+      const uint32_t lx = (ux | (ux >> 1)) & 0x01010101u, ly = (uy | (uy >> 1)) & 0x01010101u;
+      // byte e of lx / ly -> the 16-bit half of slot e: v_perm_b32 selectors, 0x0c = a zero byte
+      A[m] = __builtin_bit_cast(
+          bf16x8, make_uint4(pk_mul_u16(f.d[m][0].x, __builtin_amdgcn_perm(0u, lx, 0x0c010c00u)),
+                             pk_mul_u16(f.d[m][0].y, __builtin_amdgcn_perm(0u, lx, 0x0c030c02u)),
+                             pk_mul_u16(f.d[m][1].x, __builtin_amdgcn_perm(0u, ly, 0x0c010c00u)),
+                             pk_mul_u16(f.d[m][1].y, __builtin_amdgcn_perm(0u, ly, 0x0c030c02u))));
+      // dx of windows 0..3 at bits 8e, of windows 4..7 at bits 8e + 1; gathered to bits 2e and 2e + 1 (the
+      // product's terms fall on distinct bits: no carries; the 24-bit multiply drops e = 3, taken by the shift)
+      const uint32_t E = ((ux >> 1) & 0x01010101u) | (uy & 0x02020202u);
+      const uint32_t G = ((__umul24(E, 0x1041u) >> 12) & 0x3fu) | ((E >> 18) & 0xc0u);
+      ix[m] = (int)((G & 0x55u) | ((G & 0xaau) << 7) | 0x8888u);
     }
-    bf16x8 B1 = f.b1;
-    if (t1 >= 25) B1 = __builtin_bit_cast(bf16x8, make_uint4(b1fill, b1fill, b1fill, b1fill));
+    bf16x16 B0 = __builtin_shufflevector(f.b0[0], f.b0[1], 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+    bf16x16 B1 = __builtin_shufflevector(f.b1[0], f.b1[1], 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+    if (t1 >= 25) {
+      const bf16x8 fill = __builtin_bit_cast(bf16x8, make_uint4(b1fill, b1fill, b1fill, b1fill));
+      B1 = __builtin_shufflevector(fill, fill, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+    }
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
-      acc1[m][0] = mfma16x16x32(A[m], f.b0, acc1[m][0]);
-      acc1[m][1] = mfma16x16x32(A[m], B1, acc1[m][1]);
+      acc1[m][0] = smfmac16x16x64(A[m], B0, acc1[m][0], ix[m]);
+      acc1[m][1] = smfmac16x16x64(A[m], B1, acc1[m][1], ix[m]);
     }
   };
-  // this wave's k-steps of image j (its da1 is complete: call it in step j + 1)
+  // this wave's steps of image j (its da1 is complete: call it in step j + 1)
   auto c1_image = [&](int j) {
     const int oimg = 2 * C2D_P + (j & 1) * C12_O;
     const int ximg = 2 * (C2D_P + C12_O) + (j % 3) * C12_XS;
     const int cimg = 2 * (C2D_P + C12_O) + 3 * C12_XS + (j % 3) * C1I_IMG;
-    for (int i = 0, ks = k0; i < kcnt; ++i, ks += kst) {
+    for (int i = 0, py = k0; i < kcnt; ++i, py += kst) {
       C1F f;
-      c1_read(ks, oimg, ximg, cimg, f);
-      c1_mma(ks, f);
+      c1_read(py, oimg, ximg, cimg, f);
+      c1_mma(f);
     }
   };
   if (wave < 4) {
@@ -1021,12 +1051,12 @@ static void c2_split(int B, bool dgrad, int& nd, int& ws) {
 }
 
 // fused conv2 backward + conv1 wgrad: the dgrad role also does conv1 wgrad (104 MFMAs per image on top
-// of conv2 dgrad's 396; conv2 wgrad: 304).  Wave-specialised kernel (conv12_bwd8_kernel): the conv3 bwd8
+// of conv2 dgrad's 396, 52 sparse ones in the 8-wave kernel; conv2 wgrad: 304).  Wave-specialised kernel (conv12_bwd8_kernel): the conv3 bwd8
 // batches (use_8wave); up to them the unpipelined kernel (conv12_bwd_kernel)
 static void c12_split(int B, int& nd, int& ws) {
   const int cus = num_cus();
   if (use_8wave(B)) {
-    static const double frac3 = env_real("RINGDP_C12_DGRAD_FRAC", 0.59, split_frac_ok);
+    static const double frac3 = env_real("RINGDP_C12_DGRAD_FRAC", 0.56, split_frac_ok);
     nd = clampi(((int)(frac3 * cus) + 4) / 8 * 8, 8, cus - 8);  // multiples of 8: see conv2_wgrad8_role
     ws = clampi(cdiv(B, 8), 1, cus - nd);
     return;

@@ -1,6 +1,6 @@
 // bf16 ConvNet (design: convnet_fwd.hip): what more than one of its units (convnet_fwd.hip, convnet_bwd12.hip,
 // convnet_bwd3.hip) uses on the device - the packed-weight layout, the LDS-DMA copies, the a2 and conv1 input
-// staging, the a1 / pool1-code image sizes and the phase-stamp macro.
+// staging, the sparse MFMA's wrapper, the a1 / pool1-code image sizes and the phase-stamp macro.
 #pragma once
 
 #include "device_common.h"
@@ -56,6 +56,23 @@ __device__ __forceinline__ void glds16_sv(const void* sbase, uint32_t voff, void
 // barrier for LDS hand-offs: this wave's LDS operations drained, global stores left in flight (the release
 // fence of __syncthreads() would also wait for those)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// v_smfmac_f32_16x16x64_bf16, D[16 x 16] += A[16 x 64, 2:4 sparse] * B[64 x 16], as measured on gfx950 by
+// tools/smfmac_probe.hip (profiles/r10/c3_wgrad_sparse/probe.md); it issues at the dense 16x16x32's rate.
+//   A (8 bf16 per lane): lane l holds row l % 16.  Slots 2r, 2r+1 are the two kept values of the four dense
+//     columns k = 16 (l / 16) + 4r .. + 3, r = 0..3.
+//   index VGPR of the same lane: bits [2e+1 : 2e] = which of its four columns slot e stands for.  abid = 0 takes
+//     these 16 bits from the low half of the register, abid = 1 from the high half; cbsz is ignored.  The two
+//     indices of a group need not be ascending or distinct: every slot is simply multiplied with the B row it
+//     names (all 16 pairs checked), so one live value per group goes in slot 2r whatever its position, with a
+//     zero in slot 2r+1.
+//   B (16 bf16 per lane): lane l holds column l % 16; slots 0-7 are rows k = 8 (l / 16) + s, slots 8-15 rows
+//     32 + 8 (l / 16) + (s - 8): the B fragments of two consecutive dense 16x16x32 k-steps, back to back.
+//   D: as the dense instruction (lane l: column l % 16, rows 4 (l / 16) .. + 3).
+typedef __bf16 bf16x16 __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ f32x4 smfmac16x16x64(const bf16x8& a, const bf16x16& b, const f32x4& c, int idx) {
+  return __builtin_amdgcn_smfmac_f32_16x16x64_bf16(a, b, c, idx, 0, 0);
+}
 
 constexpr int C3_XRS = 72;  // bf16 per padded LDS row of a2 (backward wgrad role)
 
