@@ -629,11 +629,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_bwd_ds", &ops::attn_bwd_ds, "fused dP = dO V^T + softmax backward -> dS (head dim 64, Tp <= 256)");
   m.def("attn_fwd_rows", &ops::attn_fwd_rows,
         "fused attention forward on the qkv projection rows [B*T, 3*H*64]: returns [P (or, recompute=True, the "
-        "per-query log-sum-exp), out rows [B*T, H*64]]",
-        py::arg("qkv"), py::arg("B"), py::arg("T"), py::arg("H"), py::arg("scale"), py::arg("recompute") = false);
-  m.def("attn_bwd_rows", &ops::attn_bwd_rows, "fused attention backward from output-grad rows -> dqkv rows",
+        "per-query log-sum-exp), out rows [B*T, H*64]].  T > 256 (recompute=True only) runs the key-blocked "
+        "kernels; force_long runs them at any T",
+        py::arg("qkv"), py::arg("B"), py::arg("T"), py::arg("H"), py::arg("scale"), py::arg("recompute") = false,
+        py::arg("force_long") = false);
+  m.def("attn_bwd_rows", &ops::attn_bwd_rows,
+        "fused attention backward from output-grad rows -> dqkv rows.  The key-blocked kernels (T > 256, or "
+        "force_long) also need out, the forward's output rows; colsum_part is [attn_colsum_rows(B, T), 3*H*64]",
         py::arg("dout"), py::arg("qkv"), py::arg("p"), py::arg("B"), py::arg("T"), py::arg("H"), py::arg("scale"),
-        py::arg("colsum_part") = py::none());
+        py::arg("colsum_part") = py::none(), py::arg("out") = py::none(), py::arg("force_long") = false);
+  m.def("attn_colsum_rows", &ops::attn_colsum_rows, "rows of attn_bwd_rows' colsum_part", py::arg("B"), py::arg("T"),
+        py::arg("force_long") = false);
   m.def("rowsum_f32", &ops::rowsum_f32, "out[c] = sum_r part[r][c] (fp32, fixed order)");
   m.def("attn_bwd", &ops::attn_bwd,
         "fused attention backward -> dqkv rows [B*T, 3*H*Dh] (query-side dQ kernel + key-side dK/dV kernel)");

@@ -651,6 +651,15 @@ bool attn_bwd_rows_lse(const void* dout_rows, const void* qkv, const float* lse,
                        float scale, float* dsum, void* dqkv, hipStream_t s, float* colsum_part = nullptr);
 bool attn_bwd_rows(const void* dout_rows, const void* qkv, const void* p, int B, int T, int H, int Tp, int Dh,
                    float scale, float* dsum, void* dqkv, hipStream_t s);
+// any sequence length (vit_attn_long.hip; head dim 64, Tp = T rounded up to 16): key-blocked kernels with an
+// online softmax.  The backward also takes the forward's output rows (D = rowsum(dO * O)).  colsum_part
+// (nullable): [B * attn_long_blocks(Tp)][3*H*64], one partial row per (batch, 64-row block), every entry written.
+int attn_long_blocks(int Tp);
+bool attn_fwd_rows_long(const void* qkv, int B, int T, int H, int Tp, int Dh, float scale, float* lse, void* out,
+                        hipStream_t s);
+bool attn_bwd_rows_long(const void* dout_rows, const void* qkv, const float* lse, const void* out_rows, int B, int T,
+                        int H, int Tp, int Dh, float scale, float* dsum, void* dqkv, hipStream_t s,
+                        float* colsum_part = nullptr);
 void softmax_bwd(const void* p, const float* dp, int64_t rows, int T, int Tp, float scale, void* ds, hipStream_t s);
 void gelu_bwd(const void* dy, const void* pre, int64_t n, void* dx, hipStream_t s);
 void gelu_fwd(const void* x, int64_t n, void* y, hipStream_t s);  // n % 8 == 0

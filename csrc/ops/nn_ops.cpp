@@ -710,27 +710,42 @@ at::Tensor attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tenso
 }
 
 std::vector<at::Tensor> attn_fwd_rows(const at::Tensor& qkv, int64_t B, int64_t T, int64_t H, double scale,
-                                      bool recompute) {
+                                      bool recompute, bool force_long) {
   bf16_gpu(qkv, "attention qkv rows");
   RINGDP_CHECK(qkv.dim() == 2 && qkv.size(0) == B * T && qkv.size(1) % (3 * H) == 0, "attn_fwd_rows: qkv [B*T, 3*H*Dh]");
   const int64_t Dh = qkv.size(1) / (3 * H), Tp = (T + 15) / 16 * 16;
+  RINGDP_CHECK(recompute || !force_long, "attn_fwd_rows: the key-blocked kernels do not store P (recompute=True only)");
+  RINGDP_CHECK(recompute || Tp <= 256,
+               "attn_fwd_rows: the stored-P form needs T <= 256; longer sequences need recompute=True");
   at::Tensor out = at::empty({B * T, H * Dh}, qkv.options());
   if (recompute) {  // saved for the backward: per-query log-sum-exp [B*H][Tp] fp32 instead of P
     at::Tensor lse = at::empty({B * H, Tp}, qkv.options().dtype(at::kFloat));
+    if (Tp > 256 || force_long) {  // key-blocked kernels: any length
+      const bool ok = kern::attn_fwd_rows_long(qkv.data_ptr(), (int)B, (int)T, (int)H, (int)Tp, (int)Dh, (float)scale,
+                                               lse.data_ptr<float>(), out.data_ptr(), stream_of(qkv));
+      RINGDP_CHECK(ok, "attn_fwd_rows: unsupported shape (needs head dim 64)");
+      return {lse, out};
+    }
     const bool ok = kern::attn_fwd_rows_lse(qkv.data_ptr(), (int)B, (int)T, (int)H, (int)Tp, (int)Dh, (float)scale,
                                             lse.data_ptr<float>(), out.data_ptr(), stream_of(qkv));
-    RINGDP_CHECK(ok, "attn_fwd_rows: unsupported shape (needs head dim 64, T <= 256)");
+    RINGDP_CHECK(ok, "attn_fwd_rows: unsupported shape (needs head dim 64)");
     return {lse, out};
   }
   at::Tensor p = at::empty({B * H, Tp, Tp}, qkv.options());
   const bool ok = kern::attn_fwd_rows(qkv.data_ptr(), (int)B, (int)T, (int)H, (int)Tp, (int)Dh, (float)scale,
                                       p.data_ptr(), out.data_ptr(), stream_of(qkv));
-  RINGDP_CHECK(ok, "attn_fwd_rows: unsupported shape (needs head dim 64, T <= 256)");
+  RINGDP_CHECK(ok, "attn_fwd_rows: unsupported shape (the stored-P form needs head dim 64, T <= 256)");
   return {p, out};
 }
 
+int64_t attn_colsum_rows(int64_t B, int64_t T, bool force_long) {
+  const int64_t Tp = (T + 15) / 16 * 16;
+  return Tp > 256 || force_long ? B * kern::attn_long_blocks((int)Tp) : B;
+}
+
 at::Tensor attn_bwd_rows(const at::Tensor& dout, const at::Tensor& qkv, const at::Tensor& p, int64_t B, int64_t T,
-                         int64_t H, double scale, const c10::optional<at::Tensor>& colsum_part) {
+                         int64_t H, double scale, const c10::optional<at::Tensor>& colsum_part,
+                         const c10::optional<at::Tensor>& out, bool force_long) {
   bf16_gpu(dout, "attention output grad rows");
   bf16_gpu(qkv, "attention qkv rows");
   const int64_t Dh = qkv.size(1) / (3 * H), Tp = (T + 15) / 16 * 16;
@@ -739,23 +754,38 @@ at::Tensor attn_bwd_rows(const at::Tensor& dout, const at::Tensor& qkv, const at
     RINGDP_CHECK(qkv.dim() == 2 && qkv.size(0) == B * T && dout.dim() == 2 && dout.size(0) == B * T &&
                      dout.size(1) == H * Dh && p.dim() == 2 && p.size(0) == B * H && p.size(1) == Tp,
                  "attn_bwd_rows: shape mismatch");
+    const bool is_long = Tp > 256 || force_long;
     at::Tensor dqkv = at::empty_like(qkv);
     at::Tensor dsum = at::empty({B * H, Tp}, qkv.options().dtype(at::kFloat));
     float* csp = nullptr;
     if (colsum_part.has_value() && colsum_part->defined()) {  // every entry is written by one workgroup
       f32_gpu(*colsum_part, "attention dqkv column-sum partials");
-      RINGDP_CHECK(colsum_part->numel() == B * qkv.size(1) && colsum_part->is_contiguous(),
-                   "attn_bwd_rows: colsum_part must be [B, 3*H*Dh] floats");
+      RINGDP_CHECK(colsum_part->numel() == attn_colsum_rows(B, T, force_long) * qkv.size(1) &&
+                       colsum_part->is_contiguous(),
+                   "attn_bwd_rows: colsum_part must be [attn_colsum_rows(B, T), 3*H*Dh] floats");
       csp = colsum_part->data_ptr<float>();
+    }
+    if (is_long) {  // key-blocked kernels: any length; D = rowsum(dO * O) from the forward's output rows
+      RINGDP_CHECK(out.has_value() && out->defined(),
+                   "attn_bwd_rows: T > 256 needs the forward's output rows (out=)");
+      bf16_gpu(*out, "attention output rows");
+      RINGDP_CHECK(out->dim() == 2 && out->size(0) == B * T && out->size(1) == H * Dh && out->is_contiguous(),
+                   "attn_bwd_rows: out must be [B*T, H*Dh]");
+      const bool ok = kern::attn_bwd_rows_long(dout.data_ptr(), qkv.data_ptr(), p.data_ptr<float>(), out->data_ptr(),
+                                               (int)B, (int)T, (int)H, (int)Tp, (int)Dh, (float)scale,
+                                               dsum.data_ptr<float>(), dqkv.data_ptr(), stream_of(qkv), csp);
+      RINGDP_CHECK(ok, "attn_bwd_rows: unsupported shape (needs head dim 64)");
+      return dqkv;
     }
     const bool ok = kern::attn_bwd_rows_lse(dout.data_ptr(), qkv.data_ptr(), p.data_ptr<float>(), (int)B, (int)T, (int)H,
                                             (int)Tp, (int)Dh, (float)scale, dsum.data_ptr<float>(), dqkv.data_ptr(),
                                             stream_of(qkv), csp);
-    RINGDP_CHECK(ok, "attn_bwd_rows: unsupported shape (needs head dim 64, T <= 256)");
+    RINGDP_CHECK(ok, "attn_bwd_rows: unsupported shape (needs head dim 64)");
     return dqkv;
   }
   RINGDP_CHECK(!(colsum_part.has_value() && colsum_part->defined()),
                "attn_bwd_rows: column sums need the recompute (log-sum-exp) path");
+  RINGDP_CHECK(!force_long, "attn_bwd_rows: the key-blocked kernels need the log-sum-exp, not a stored P");
   bf16_gpu(p, "attention probs");
   RINGDP_CHECK(qkv.dim() == 2 && qkv.size(0) == B * T && dout.dim() == 2 && dout.size(0) == B * T &&
                    dout.size(1) == H * Dh && p.dim() == 3 && p.size(0) == B * H && p.size(1) == Tp && p.size(2) == Tp,
@@ -764,7 +794,7 @@ at::Tensor attn_bwd_rows(const at::Tensor& dout, const at::Tensor& qkv, const at
   at::Tensor dsum = at::empty({B * H, Tp}, qkv.options().dtype(at::kFloat));
   const bool ok = kern::attn_bwd_rows(dout.data_ptr(), qkv.data_ptr(), p.data_ptr(), (int)B, (int)T, (int)H, (int)Tp,
                                       (int)Dh, (float)scale, dsum.data_ptr<float>(), dqkv.data_ptr(), stream_of(qkv));
-  RINGDP_CHECK(ok, "attn_bwd_rows: unsupported shape (needs head dim 64, T <= 256)");
+  RINGDP_CHECK(ok, "attn_bwd_rows: unsupported shape (the stored-P form needs head dim 64, T <= 256)");
   return dqkv;
 }
 

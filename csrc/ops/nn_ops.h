@@ -89,10 +89,13 @@ at::Tensor attn_bwd_ds(const at::Tensor& dout, const at::Tensor& v, const at::Te
 at::Tensor attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                     const at::Tensor& p, int64_t B, int64_t T, int64_t H, double scale);
 std::vector<at::Tensor> attn_fwd_rows(const at::Tensor& qkv, int64_t B, int64_t T, int64_t H, double scale,
-                                      bool recompute = false);
+                                      bool recompute = false, bool force_long = false);
+// rows of attn_bwd_rows' colsum_part: B for T <= 256, B * (64-row blocks) for the key-blocked kernels
+int64_t attn_colsum_rows(int64_t B, int64_t T, bool force_long = false);
 at::Tensor attn_bwd_rows(const at::Tensor& dout, const at::Tensor& qkv, const at::Tensor& p, int64_t B, int64_t T,
                          int64_t H, double scale,
-                         const c10::optional<at::Tensor>& colsum_part = c10::nullopt);
+                         const c10::optional<at::Tensor>& colsum_part = c10::nullopt,
+                         const c10::optional<at::Tensor>& out = c10::nullopt, bool force_long = false);
 std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, int64_t T,
                                  double scale);
 at::Tensor softmax_bwd(const at::Tensor& p, const at::Tensor& dp, int64_t T, double scale);

@@ -17,6 +17,10 @@ GPU the masks come from ``ringdp.ops.dropout`` (one ``rng_tick`` per forward, hi
 the dropout and the drop-path of a branch are one kernel, and the block takes the unfused linears instead of
 MLPF / MLPF8, which costs the separate GELU-backward pass.  With everything at 0, or in ``eval()``, the path and
 the launches are the ones described above.
+
+Fine-tuning at another resolution: ``load_state_dict(sd, resize_pos_embedding=True)`` resizes the checkpoint's
+position embedding (``interpolate_pos_embedding``); sequences of more than 256 tokens (384x384: 577) run the
+key-blocked attention kernels.
 """
 from __future__ import annotations
 
@@ -143,17 +147,39 @@ class Encoder(nn.Module):
         return self.ln(self.layers(self.dropout(x + self.pos_embedding)))
 
 
+def interpolate_pos_embedding(pos: torch.Tensor, new_seq_length: int, *, interpolation: str = "bicubic") -> torch.Tensor:
+    """Resize a position embedding ``[1, 1 + n*n, D]`` to ``[1, 1 + m*m, D]`` (``new_seq_length = 1 + m*m``) for
+    fine-tuning at another resolution: the class-token row is copied and the ``n x n`` grid of patch positions is
+    resized to ``m x m`` with ``align_corners=True``, as torchvision's ``interpolate_embeddings`` does.  Runs in
+    fp32 on the tensor's device (a one-off at load time); equal lengths return ``pos`` itself."""
+    if pos.dim() != 3 or pos.shape[0] != 1:
+        raise ValueError(f"interpolate_pos_embedding: expected [1, seq_length, D], got {tuple(pos.shape)}")
+    seq_length, dim = pos.shape[1], pos.shape[2]
+    n, m = math.isqrt(max(seq_length - 1, 0)), math.isqrt(max(new_seq_length - 1, 0))
+    if seq_length < 2 or n * n != seq_length - 1:
+        raise ValueError(f"interpolate_pos_embedding: sequence length {seq_length} is not 1 + a square")
+    if new_seq_length < 2 or m * m != new_seq_length - 1:
+        raise ValueError(f"interpolate_pos_embedding: sequence length {new_seq_length} is not 1 + a square")
+    if new_seq_length == seq_length:
+        return pos
+    grid = pos[:, 1:].float().permute(0, 2, 1).reshape(1, dim, n, n)
+    kw = {} if interpolation in ("nearest", "area", "nearest-exact") else {"align_corners": True}
+    grid = nn.functional.interpolate(grid, size=(m, m), mode=interpolation, **kw)
+    grid = grid.reshape(1, dim, m * m).permute(0, 2, 1)
+    return torch.cat([pos[:, :1].float(), grid], dim=1).to(pos.dtype)
+
+
 class VisionTransformer(nn.Module):
     def __init__(self, image_size: int = 224, patch_size: int = 16, num_layers: int = 12, num_heads: int = 12,
                  hidden_dim: int = 768, mlp_dim: int = 3072, num_classes: int = 1000, dropout: float = 0.0,
-                 stochastic_depth_prob: float = 0.0):
+                 stochastic_depth_prob: float = 0.0, attention_dropout: float = 0.0):
         super().__init__()
         self.image_size, self.patch_size, self.hidden_dim = image_size, patch_size, hidden_dim
         self.conv_proj = nn.Conv2d(3, hidden_dim, kernel_size=patch_size, stride=patch_size)
         seq_length = (image_size // patch_size) ** 2 + 1
         self.class_token = nn.Parameter(torch.zeros(1, 1, hidden_dim))
         self.encoder = Encoder(seq_length, num_layers, num_heads, hidden_dim, mlp_dim, dropout,
-                               stochastic_depth_prob=stochastic_depth_prob)
+                               attention_dropout=attention_dropout, stochastic_depth_prob=stochastic_depth_prob)
         self.seq_length = seq_length
         self.heads = nn.Sequential(OrderedDict(head=nn.Linear(hidden_dim, num_classes)))
         fan_in = 3 * patch_size * patch_size
@@ -166,6 +192,17 @@ class VisionTransformer(nn.Module):
         if x.is_cuda:
             return self.forward_rows(x)
         return self.reference_forward(x)
+
+    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False, *,
+                        resize_pos_embedding: bool = False):
+        """``nn.Module.load_state_dict``; with ``resize_pos_embedding=True`` a checkpoint trained at another
+        resolution loads: its ``encoder.pos_embedding`` is resized (a copy; see ``interpolate_pos_embedding``)."""
+        key = "encoder.pos_embedding"
+        if resize_pos_embedding and key in state_dict and \
+                state_dict[key].shape != self.encoder.pos_embedding.shape:
+            state_dict = OrderedDict(state_dict)
+            state_dict[key] = interpolate_pos_embedding(state_dict[key], self.seq_length)
+        return super().load_state_dict(state_dict, strict=strict, assign=assign)
 
     def reference_forward(self, x: torch.Tensor) -> torch.Tensor:
         n = x.shape[0]

@@ -21,7 +21,8 @@ from . import grad_buffer
 # RINGDP_ATTN_UNFUSED=1: attention forward as two GEMMs + a softmax pass (the path the fused kernel replaced)
 _ATTN_UNFUSED = os.environ.get("RINGDP_ATTN_UNFUSED", "0") == "1"
 _ATTN_BWD_GEMMS = os.environ.get("RINGDP_ATTN_BWD_GEMMS", "0") == "1"  # dS kernel + batched GEMMs (A/B runs)
-# fused attention saves the per-query log-sum-exp and the backward recomputes P (RINGDP_ATTN_RECOMPUTE=0: store P)
+# fused attention saves the per-query log-sum-exp and the backward recomputes P (RINGDP_ATTN_RECOMPUTE=0: store P;
+# above 256 tokens only the recompute form has fused kernels, and 0 selects the GEMM path)
 _ATTN_RECOMPUTE = os.environ.get("RINGDP_ATTN_RECOMPUTE", "1") == "1"
 # LayerNorm backward also emits the column sums of dx (the producing linear's bias gradient)
 _LN_COLSUM = os.environ.get("RINGDP_LN_COLSUM", "0") == "1"
@@ -591,11 +592,15 @@ class AttentionF(torch.autograd.Function):
     def forward(ctx, qkv, B: int, T: int, H: int):
         Tp = _tp(T)
         Dh = qkv.shape[1] // (3 * H)
-        if Dh == 64 and Tp <= 256 and not _ATTN_UNFUSED and not _ATTN_BWD_GEMMS:
-            # fused kernels straight on the projection rows: no head-major split / merge passes
+        if Dh == 64 and (Tp <= 256 or _ATTN_RECOMPUTE) and not _ATTN_UNFUSED and not _ATTN_BWD_GEMMS:
+            # fused kernels straight on the projection rows: no head-major split / merge passes.  Tp > 256 runs
+            # the key-blocked kernels (log-sum-exp only), whose backward takes D = rowsum(dO * O) from `out`
             scale = 1.0 / math.sqrt(Dh)
             p, out = C.attn_fwd_rows(qkv, B, T, H, scale, _ATTN_RECOMPUTE)  # p: P, or the log-sum-exp
-            ctx.save_for_backward(qkv, p)
+            if Tp > 256:
+                ctx.save_for_backward(qkv, p, out)
+            else:
+                ctx.save_for_backward(qkv, p)
             ctx.cfg = (B, T, H, Tp, scale)
             ctx.rows = True
             return out
@@ -619,16 +624,18 @@ class AttentionF(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         if ctx.rows:
-            qkv, p = ctx.saved_tensors
+            qkv, p, *rest = ctx.saved_tensors
+            out = rest[0] if rest else None  # saved for Tp > 256 only
             B, T, H, Tp, scale = ctx.cfg
             if p.dtype == torch.float32 and not _FP8["on"]:
-                # the kernels also sum their dq / dk / dv rows per batch: the qkv projection's bias gradient is
-                # then one [B, 3D] -> [3D] reduction in LinearF's backward instead of a pass over dqkv
-                part = torch.empty(B, qkv.shape[1], device=qkv.device, dtype=torch.float32)
-                dqkv = C.attn_bwd_rows(dout.contiguous(), qkv, p, B, T, H, scale, part)
+                # the kernels also sum their dq / dk / dv rows per batch (per batch and 64-row block for
+                # Tp > 256): the qkv projection's bias gradient is then one [rows, 3D] -> [3D] reduction in
+                # LinearF's backward instead of a pass over dqkv
+                part = torch.empty(C.attn_colsum_rows(B, T), qkv.shape[1], device=qkv.device, dtype=torch.float32)
+                dqkv = C.attn_bwd_rows(dout.contiguous(), qkv, p, B, T, H, scale, part, out)
                 dqkv._ringdp_colsum_part = part
                 return dqkv, None, None, None
-            return C.attn_bwd_rows(dout.contiguous(), qkv, p, B, T, H, scale), None, None, None
+            return C.attn_bwd_rows(dout.contiguous(), qkv, p, B, T, H, scale, None, out), None, None, None
         q, k, v, p = ctx.saved_tensors
         B, T, H, Tp, scale = ctx.cfg
         BH, _, Dh = q.shape
