@@ -558,10 +558,33 @@ std::vector<at::Tensor> layernorm_fwd_q8(const at::Tensor& x, const at::Tensor& 
   kern::layernorm_fwd_q8(x.data_ptr(), w.data_ptr<float>(), b.data_ptr<float>(), rows, (int)D, (float)eps,
                          stats.data_ptr<float>(), hist.data_ptr<float>(), q.data_ptr(), qt.data_ptr(),
                          scale.data_ptr<float>(), hist.data_ptr<float>() + 1, stream_of(x));
+  // the kernel takes 64 * (D + 4) bytes of dynamic LDS (131,328 B at D = 2048): a launch the runtime refuses must
+  // not leave stats / q / qt unwritten without a word
+  RINGDP_HIP_CHECK(hipGetLastError());
   return {stats, q, qt, scale};
 }
 
 int64_t layernorm_q8_slots(int64_t rows) { return kern::layernorm_q8_blocks(rows); }
+
+namespace {
+
+// the backward kernel reads 8-wide vectors, keeps red[4][2048] in LDS and indexes w / stats / dw / db by D and rows
+void ln_bwd_shapes(const at::Tensor& w, const at::Tensor& stats, const at::Tensor& dw, const at::Tensor& db,
+                   int64_t rows, int64_t D) {
+  f32_gpu(w, "layernorm weight");
+  RINGDP_CHECK(D % 8 == 0 && D <= 2048, "layernorm backward: D must be a multiple of 8, at most 2048");
+  RINGDP_CHECK(w.numel() == D && dw.numel() == D && db.numel() == D, "layernorm backward: w / dw / db must hold D floats");
+  RINGDP_CHECK(stats.numel() == 2 * rows, "layernorm backward: stats must hold (mean, rstd) per row");
+}
+
+// head-major tensors [B*H][Tp][Dh] against B and T
+void head_shapes(const at::Tensor& t, int64_t B, int64_t T, const char* name) {
+  RINGDP_CHECK(t.dim() == 3 && B > 0 && T > 0, name, ": expected [B*H, Tp, Dh], B > 0, T > 0");
+  RINGDP_CHECK(t.size(0) % B == 0 && T <= t.size(1) && t.size(2) % 8 == 0, name,
+               ": B must divide B*H, T <= Tp, Dh % 8 == 0");
+}
+
+}  // namespace
 
 std::vector<at::Tensor> layernorm_bwd_colsum(const at::Tensor& dy, const at::Tensor& x, const at::Tensor& stats,
                                              const at::Tensor& w, const c10::optional<at::Tensor>& dres, at::Tensor dw,
@@ -572,7 +595,8 @@ std::vector<at::Tensor> layernorm_bwd_colsum(const at::Tensor& dy, const at::Ten
   f32_gpu(dw, "layernorm dweight");
   f32_gpu(db, "layernorm dbias");
   const int64_t D = x.size(-1), rows = x.numel() / D;
-  RINGDP_CHECK(dy.sizes() == x.sizes() && D % 4 == 0, "layernorm backward: shape mismatch");
+  RINGDP_CHECK(dy.sizes() == x.sizes(), "layernorm backward: shape mismatch");
+  ln_bwd_shapes(w, stats, dw, db, rows, D);
   const void* dr = nullptr;
   if (dres.has_value() && dres->defined()) {
     bf16_gpu(*dres, "layernorm residual grad");
@@ -597,6 +621,7 @@ at::Tensor layernorm_bwd(const at::Tensor& dy, const at::Tensor& x, const at::Te
   f32_gpu(db, "layernorm dbias");
   const int64_t D = x.size(-1), rows = x.numel() / D;
   RINGDP_CHECK(dy.sizes() == x.sizes(), "layernorm backward: shape mismatch");
+  ln_bwd_shapes(w, stats, dw, db, rows, D);
   const void* dr = nullptr;
   if (dres.has_value() && dres->defined()) {
     bf16_gpu(*dres, "layernorm residual grad");
@@ -614,6 +639,7 @@ at::Tensor layernorm_bwd(const at::Tensor& dy, const at::Tensor& x, const at::Te
 std::tuple<at::Tensor, at::Tensor, at::Tensor> qkv_split(const at::Tensor& qkv, int64_t B, int64_t T, int64_t H,
                                                          int64_t Tp) {
   bf16_gpu(qkv, "qkv");
+  RINGDP_CHECK(B > 0 && T > 0 && H > 0, "qkv_split: B, T, H must be positive");
   const int64_t D3 = qkv.size(-1), Dh = D3 / 3 / H;
   RINGDP_CHECK(qkv.numel() == B * T * D3 && Dh * 3 * H == D3 && Dh % 8 == 0 && Tp >= T, "qkv_split: bad shapes");
   auto opt = qkv.options();
@@ -627,6 +653,8 @@ at::Tensor qkv_merge(const at::Tensor& dq, const at::Tensor& dk, const at::Tenso
   bf16_gpu(dq, "dq");
   bf16_gpu(dk, "dk");
   bf16_gpu(dv, "dv");
+  head_shapes(dq, B, T, "qkv_merge");
+  RINGDP_CHECK(dk.sizes() == dq.sizes() && dv.sizes() == dq.sizes(), "qkv_merge: dq, dk, dv must have one shape");
   const int64_t BH = dq.size(0), Tp = dq.size(1), Dh = dq.size(2), H = BH / B;
   at::Tensor out = at::empty({B * T, 3 * H * Dh}, dq.options());
   kern::qkv_merge(dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), (int)B, (int)T, (int)H, (int)Dh, (int)Tp,
@@ -636,6 +664,7 @@ at::Tensor qkv_merge(const at::Tensor& dq, const at::Tensor& dk, const at::Tenso
 
 at::Tensor heads_to_rows(const at::Tensor& o, int64_t B, int64_t T) {
   bf16_gpu(o, "attention output");
+  head_shapes(o, B, T, "heads_to_rows");
   const int64_t BH = o.size(0), Tp = o.size(1), Dh = o.size(2), H = BH / B;
   at::Tensor out = at::empty({B * T, H * Dh}, o.options());
   kern::heads_to_rows(o.data_ptr(), (int)B, (int)T, (int)H, (int)Dh, (int)Tp, out.data_ptr(), stream_of(o));
@@ -644,7 +673,10 @@ at::Tensor heads_to_rows(const at::Tensor& o, int64_t B, int64_t T) {
 
 at::Tensor rows_to_heads(const at::Tensor& rows, int64_t B, int64_t T, int64_t H, int64_t Tp) {
   bf16_gpu(rows, "token rows");
+  RINGDP_CHECK(B > 0 && T > 0 && H > 0, "rows_to_heads: B, T, H must be positive");
   const int64_t D = rows.size(-1), Dh = D / H;
+  RINGDP_CHECK(D % H == 0 && Dh % 8 == 0 && T <= Tp && rows.numel() == B * T * D,
+               "rows_to_heads: expected [B*T, H*Dh] rows, Dh % 8 == 0, T <= Tp");
   at::Tensor out = at::empty({B * H, Tp, Dh}, rows.options());
   kern::rows_to_heads(rows.data_ptr(), (int)B, (int)T, (int)H, (int)Dh, (int)Tp, out.data_ptr(), stream_of(rows));
   return out;
@@ -652,7 +684,9 @@ at::Tensor rows_to_heads(const at::Tensor& rows, int64_t B, int64_t T, int64_t H
 
 at::Tensor softmax_fwd(const at::Tensor& scores, int64_t T, double scale) {
   f32_gpu(scores, "attention scores");
+  RINGDP_CHECK(scores.dim() >= 1 && scores.size(-1) > 0, "softmax_fwd: expected [..., Tp] scores");
   const int64_t Tp = scores.size(-1), rows = scores.numel() / Tp;
+  RINGDP_CHECK(0 < T && T <= Tp && rows % Tp == 0, "softmax_fwd: 0 < T <= Tp, whole [Tp, Tp] heads");
   at::Tensor p = at::empty(scores.sizes(), scores.options().dtype(at::kBFloat16));
   kern::softmax_fwd(scores.data_ptr<float>(), rows, (int)T, (int)Tp, (float)scale, p.data_ptr(), stream_of(scores));
   return p;
@@ -801,7 +835,9 @@ at::Tensor attn_bwd_rows(const at::Tensor& dout, const at::Tensor& qkv, const at
 at::Tensor softmax_bwd(const at::Tensor& p, const at::Tensor& dp, int64_t T, double scale) {
   bf16_gpu(p, "attention probs");
   f32_gpu(dp, "attention probs grad");
+  RINGDP_CHECK(p.dim() >= 1 && p.size(-1) > 0 && dp.sizes() == p.sizes(), "softmax_bwd: p and dp must have one shape");
   const int64_t Tp = p.size(-1), rows = p.numel() / Tp;
+  RINGDP_CHECK(0 < T && T <= Tp && rows % Tp == 0, "softmax_bwd: 0 < T <= Tp, whole [Tp, Tp] heads");
   at::Tensor ds = at::empty_like(p);
   kern::softmax_bwd(p.data_ptr(), dp.data_ptr<float>(), rows, (int)T, (int)Tp, (float)scale, ds.data_ptr(),
                     stream_of(p));
@@ -833,7 +869,10 @@ at::Tensor assemble_tokens_bwd(const at::Tensor& dout, at::Tensor dpos, at::Tens
   bf16_gpu(dout, "token grad");
   f32_gpu(dpos, "position grad");
   f32_gpu(dcls, "class token grad");
+  RINGDP_CHECK(dout.dim() == 3, "assemble_tokens_bwd: expected a [B, T, D] token gradient");
   const int64_t B = dout.size(0), T = dout.size(1), D = dout.size(2);
+  RINGDP_CHECK(T >= 2 && dpos.numel() == T * D && dcls.numel() == D,
+               "assemble_tokens_bwd: T >= 2, dpos must hold T*D floats and dcls D");
   at::Tensor dp = at::empty({B, T - 1, D}, dout.options());
   kern::assemble_tokens_bwd(dout.data_ptr(), (int)B, (int)(T - 1), (int)D, dp.data_ptr(), dpos.data_ptr<float>(),
                             dcls.data_ptr<float>(), stream_of(dout));
@@ -842,7 +881,9 @@ at::Tensor assemble_tokens_bwd(const at::Tensor& dout, at::Tensor dpos, at::Tens
 
 at::Tensor cls_rows(const at::Tensor& x, int64_t B, int64_t T, bool reverse) {
   bf16_gpu(x, "token rows");
+  RINGDP_CHECK(B > 0 && T > 0 && x.dim() >= 1, "cls_rows: B and T must be positive");
   const int64_t D = x.size(-1);
+  RINGDP_CHECK(x.numel() == (reverse ? B * D : B * T * D), "cls_rows: expected ", reverse ? "[B, D]" : "[B*T, D]", " rows");
   at::Tensor y = reverse ? at::zeros({B, T, D}, x.options()) : at::empty({B, D}, x.options());
   kern::cls_rows(x.data_ptr(), (int)B, (int)T, (int)D, y.data_ptr(), reverse, stream_of(x));
   return y;
