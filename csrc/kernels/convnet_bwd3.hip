@@ -677,7 +677,9 @@ __device__ __forceinline__ void c3_pool2_bwd(const C3Pool2Map& m, const float* D
     masked_add(g, pa, m.sh[i][1], qa);
     masked_add(g, nb2, m.sh[i][2], eb);
     masked_add(g, pb, m.sh[i][3], qb);
-    dst[i * 16] = bf16x4{(bf16)g[0], (bf16)g[1], (bf16)g[2], (bf16)g[3]};
+    // nontemporal: dz2 (15.5 KB per image, read once by the conv12 backward) streams past the Infinity Cache
+    // (B=65536: this kernel 927 -> 915 us, conv12_bwd8_kernel unchanged; profiles/r15/head_bytes/README.md)
+    __builtin_nontemporal_store(bf16x4{(bf16)g[0], (bf16)g[1], (bf16)g[2], (bf16)g[3]}, &dst[i * 16]);
     pa = na;
     pb = nb2;
     qa = ea;
@@ -1113,6 +1115,11 @@ void cn_conv3_fc_bwd(const void* a2, const uint8_t* idx2, const void* a3, const 
                                                        static_cast<bf16*>(dz2), B, c3_slabs, ws, nd,
                                                        c3_dgrad_images(B, nd), fs, fc_slabs, fc_imgs_host(B));
   } else {
+    // Second pass over a3 after fc1_fwd_kernel, in the same direction.  Opposite directions (this launch by
+    // descending image group, or fc1_fwd_kernel descending by workgroup and by group inside it) measured no
+    // different at B=65536: both launches are 512 workgroups, all resident at once (2 per CU), so the order of
+    // workgroups is no order in time, and the order of images inside a workgroup here is the order of the
+    // fp32 sums (profiles/r15/head_bytes/README.md).
     if (ce)
       fc_bwd_kernel<true><<<fs, 256, 0, s>>>(a3b, pk, nullptr, static_cast<bf16*>(da3m), fc_slabs, B, fc_imgs_host(B), cef);
     else

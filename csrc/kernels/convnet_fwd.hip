@@ -298,6 +298,8 @@ constexpr int C1F_MT = 11;  // m-tiles per wave (wave 3: 10)
 constexpr int C1F_CS = 1048;
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));  // the builtin nontemporal store takes native vectors
+typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 // PACK: this launch also packs every layer's weights (cn_pack_weights) for the kernels after it: workgroups
 // >= conv_blocks do only that, and the conv1 workgroups build their own fragments from the fp32 masters
 // (one launch per step fewer; at the reference batch every launch is ~5 us of a ~100 us step).
@@ -761,8 +763,8 @@ __device__ __forceinline__ void ff_pool2(const bf16* Cs, bf16* X3b, bf16* __rest
     bf16x8 v;
     uint2 code;
     pool2_code8(Cs + (p + y) * C2_CRS + c, C2_CRS, 11, v, code);  // row y * 11 + (p - 10 y) = p + y
-    da[it] = v;
-    di[it] = code;
+    __builtin_nontemporal_store(v, &da[it]);  // streamed: see ff_producer's a1 / idx1 copy-out
+    __builtin_nontemporal_store(u32x2v{code.x, code.y}, reinterpret_cast<u32x2v*>(&di[it]));
     *reinterpret_cast<bf16x8*>(X3b + p * C3F_XRS + c) = v;
   }
 }
@@ -883,13 +885,18 @@ __device__ __forceinline__ void ff_producer(char* smem, const void* __restrict__
           acc[mt][1] = mfma16x16x32(bw2[1][ks], a, acc[mt][1]);
         }
       }
-      // a1 / idx1 to HBM while the MFMAs drain
-      uint4* og = reinterpret_cast<uint4*>(a1 + (int64_t)b * C1A_IMG);
+      // a1 / idx1 to HBM while the MFMAs drain.  These and pool2's a2 / idx2 (33.5 of the 39.5 KB an image
+      // writes) are next read by the backward kernels, after more traffic than the Infinity Cache holds, so
+      // they are nontemporal stores: as plain stores they were still being written back to HBM while
+      // fc1_fwd_kernel streamed a3 (B=65536: that pass 94 -> 53 us, this kernel unchanged;
+      // profiles/r15/head_bytes/README.md).  a3 / idx3 stay plain: nontemporal 2-B / 1-B stores cost this
+      // kernel 9 us.
+      u32x4v* og = reinterpret_cast<u32x4v*>(a1 + (int64_t)b * C1A_IMG);
       for (int c = tid; c < C1A_IMG / 8; c += 256)
-        og[c] = *reinterpret_cast<const uint4*>(X2 + (c >> 2) * C2_XRS + (c & 3) * 8);
-      const uint4* cs = reinterpret_cast<const uint4*>(CT);
-      uint4* cg = reinterpret_cast<uint4*>(idx1 + (int64_t)b * C1I_IMG);
-      for (int c = tid; c < C1I_IMG / 16; c += 256) cg[c] = cs[c];
+        __builtin_nontemporal_store(*reinterpret_cast<const u32x4v*>(X2 + (c >> 2) * C2_XRS + (c & 3) * 8), og + c);
+      const u32x4v* cs = reinterpret_cast<const u32x4v*>(CT);
+      u32x4v* cg = reinterpret_cast<u32x4v*>(idx1 + (int64_t)b * C1I_IMG);
+      for (int c = tid; c < C1I_IMG / 16; c += 256) __builtin_nontemporal_store(cs[c], cg + c);
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt) {
         const int m = opos2[mt];
