@@ -615,6 +615,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("cutmix_alpha"), py::arg("prob"), py::arg("switch_prob"));
   m.def("mix_images", &ops::mix_images, "(x mixed with x.flip(0) as the records say, y.flip(0))", py::arg("x"),
         py::arg("y"), py::arg("rec"));
+  m.def("crop_draw", &ops::crop_draw,
+        "random-resized-crop records int32 [R, 8] = {y0, x0, h, w, flip, erase rows, erase columns, 0}; scale=None: "
+        "the whole image",
+        py::arg("snapshot"), py::arg("R"), py::arg("H"), py::arg("W"), py::arg("S"), py::arg("scale"),
+        py::arg("ratio"), py::arg("hflip"), py::arg("erase_prob"), py::arg("erase_scale"), py::arg("erase_ratio"));
+  m.def("resize_crop", &ops::resize_crop,
+        "(crop + bilinear resize to S x S + flip + normalise + erase of x[idx] as the records say, labels[idx])",
+        py::arg("x"), py::arg("labels"), py::arg("idx"), py::arg("rec"), py::arg("S"),
+        py::arg("mean") = std::vector<double>{}, py::arg("std") = std::vector<double>{},
+        py::arg("channels_last") = false, py::arg("out_dtype") = at::kFloat);
   m.def("layernorm_fwd", &ops::layernorm_fwd);
   m.def("layernorm_bwd", &ops::layernorm_bwd);
   m.def("layernorm_fwd_q8", &ops::layernorm_fwd_q8, "layernorm forward with e4m3 outputs (q, q^T) at a delayed scale");

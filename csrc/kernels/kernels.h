@@ -711,6 +711,26 @@ struct AugNorm {
 void gather_augment(const uint8_t* x, const int64_t* labels, const int64_t* idx, int B, int H, int W, int C,
                     int pad, bool flip, const AugNorm& nrm, uint64_t seed, bool nhwc, int out_kind, void* out,
                     int64_t* yout, hipStream_t s);
+// ---------------------------------------------------------------- random-resized-crop + resize (resize_crop.hip)
+// Records: int32 [R, 8] = {y0, x0, h, w (crop box in source pixels), flip, ey0 | ey1 << 16, ex0 | ex1 << 16 (erase
+// box, half-open, output coordinates), 0}.  Drawn with Philox4x32-10, key = seed, counter = (record, step lo,
+// step hi, round): rounds 0..9 the crop attempts, 10 flip / erase decisions, 11..20 the erase attempts.
+struct CropDrawArgs {
+  int R, H, W, S;
+  int crop, hflip;                    // crop == 0: the whole image
+  float scale0, scale1, ratio0, ratio1;
+  float erase_prob, escale0, escale1, eratio0, eratio1;
+};
+void crop_draw(const uint64_t* snapshot, const CropDrawArgs& a, int32_t* rec, hipStream_t s);
+constexpr int kResizeMaxSourceBytes = 32 * 1024;  // H * W * C of one image: it is staged in LDS
+constexpr int kResizeMaxSize = 1024;              // S
+// out[b] = normalise(flip(bilinear(x[idx[b]][box] -> S x S))) with the erase box zeroed, as record b (rec_elem) or
+// record 0 says; x uint8 [N, H, W, C], out [B, C, S, S] (or [B, S, S, C] when nhwc) of fp32 / bf16.
+// yout[b] = labels[idx[b]] when labels != nullptr.  Records and indices are clamped into range by the kernel.
+void resize_crop(const uint8_t* x, const int64_t* labels, const int64_t* idx, const int32_t* rec, bool rec_elem,
+                 int B, int64_t N, int H, int W, int C, int S, const AugNorm& nrm, bool nhwc, bool out_bf16,
+                 void* out, int64_t* yout, hipStream_t s);
+
 // Synthetic MNIST-shaped batch (u8 images + labels) from a counter-based hash (deterministic).
 void synth_u8_images(uint8_t* x, int64_t* labels, int B, int HW, int num_classes, uint64_t seed,
                      hipStream_t s);

@@ -67,6 +67,19 @@ at::Tensor mix_draw(const at::Tensor& snapshot, int64_t R, int64_t H, int64_t W,
                     double cutmix_alpha, double prob, double switch_prob);
 std::tuple<at::Tensor, at::Tensor> mix_images(const at::Tensor& x, const at::Tensor& y, const at::Tensor& rec);
 
+// Random-resized-crop + bilinear resize for the device loader (resize_crop_ops.cpp).  crop_draw: int32 [R, 8] records
+// {y0, x0, h, w, flip, erase rows, erase columns, 0} from an rng_tick snapshot; scale = nullopt: the whole image.
+// resize_crop: (out [B, C, S, S] fp32 / bf16 in NCHW or channels-last memory, labels[idx]) from the uint8 dataset
+// x [N, H, W] or [N, H, W, C] and records [1, 8] or [B, 8].
+typedef std::pair<double, double> Range;
+at::Tensor crop_draw(const at::Tensor& snapshot, int64_t R, int64_t H, int64_t W, int64_t S,
+                     const c10::optional<Range>& scale, Range ratio, bool hflip, double erase_prob, Range erase_scale,
+                     Range erase_ratio);
+std::tuple<at::Tensor, at::Tensor> resize_crop(const at::Tensor& x, const c10::optional<at::Tensor>& labels,
+                                               const at::Tensor& idx, const at::Tensor& rec, int64_t S,
+                                               std::vector<double> mean, std::vector<double> std, bool channels_last,
+                                               at::ScalarType out_dtype);
+
 std::tuple<at::Tensor, at::Tensor> layernorm_fwd(const at::Tensor& x, const at::Tensor& w, const at::Tensor& b,
                                                  double eps);
 // LayerNorm forward writing e4m3 (delayed scaling, hist = [amax, per-64-row-block maxima]): [stats, q, qt, scale]

@@ -35,6 +35,11 @@ OUT_DIR = ROOT / "ringdp"
 EXT_NAME = "_C"
 ARCH = os.environ.get("RINGDP_ARCH", "gfx950")
 ROCM = Path(os.environ.get("ROCM_PATH", "/opt/rocm"))
+# Extra hipcc flags of single units.  resize_crop.hip: plain fp32 interpolation arithmetic, kept on the scalar
+# v_fma_f32 / v_mul_f32 forms (no packed fp32 pairs).
+UNIT_FLAGS = {
+    "resize_crop.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 
 
 def _torch_paths():
@@ -85,7 +90,7 @@ def _compile_cmd(src: Path, obj: Path, sanitize: str | None = None):
         # Device code: pure HIP for CDNA4.  No torch headers here on purpose.
         return [
             _hipcc(), f"--offload-arch={ARCH}", "-O3", "-fno-gpu-rdc", "-munsafe-fp-atomics",
-            *common, "-c", str(src), "-o", str(obj),
+            *UNIT_FLAGS.get(src.name, []), *common, "-c", str(src), "-o", str(obj),
         ]
     defs = [
         "-D__HIP_PLATFORM_AMD__=1",  # selects the AMD flavour of the HIP runtime headers

@@ -18,6 +18,10 @@ re-raised in the main process with its traceback, a worker that dies is reported
 batch is ONE HIP launch (``C.gather_augment``: index gather + random crop / flip + ToTensor +
 Normalize, writing fp32/bf16 NCHW/NHWC or raw uint8 for the ConvNet, whose first kernel fuses the
 normalisation).  No host work per step, so the loop can be captured in a hipGraph.
+With ``resize=S`` a batch is three launches instead - ``rng_tick``, ``C.crop_draw`` and ``C.resize_crop``
+(``ringdp.ops.resize_crop``): a random-resized crop per sample, bilinear resize to ``S x S``, flip, normalise and
+random erasing, drawn on the device from the ``(seed, step)`` state of ``ringdp.random``, so a captured batch
+re-augments on every replay.  ``eval()`` switches to the plain resize of the whole image (one launch, no draw).
 """
 from __future__ import annotations
 
@@ -283,12 +287,22 @@ class _MultiProcessIter:
 
 
 class DeviceLoader:
-    """HBM-resident dataset + one fused gather/augment HIP launch per batch (see module doc)."""
+    """HBM-resident dataset + one fused gather/augment HIP launch per batch (see module doc).
+
+    ``resize=S`` (off by default) turns the batch into ``[B, C, S, S]`` images: ``crop_scale`` / ``crop_ratio`` are
+    torchvision's ``RandomResizedCrop`` ranges (``crop_scale=None``: resize only), ``erase_prob`` / ``erase_scale`` /
+    ``erase_ratio`` its ``RandomErasing`` with value 0; ``hflip`` then flips with probability 0.5 from the same
+    draw, and ``seed`` / ``step_seed`` play no part: the randomness is ``ringdp.random``'s device state.
+    ``channels_last=True`` gives the channels-last memory format.  ``eval()`` / ``train()`` switch the augmentation
+    off and on."""
 
     def __init__(self, dataset, batch_size: int, device, sampler: Optional[DistributedSampler] = None,
                  drop_last: bool = False, crop_padding: int = 0, hflip: bool = False,
                  mean: Optional[Sequence[float]] = None, std: Optional[Sequence[float]] = None,
-                 out_dtype: torch.dtype = torch.float32, channels_last: bool = False, seed: int = 0):
+                 out_dtype: torch.dtype = torch.float32, channels_last: bool = False, seed: int = 0,
+                 resize: Optional[int] = None, crop_scale: Optional[Sequence[float]] = (0.08, 1.0),
+                 crop_ratio: Sequence[float] = (3 / 4, 4 / 3), erase_prob: float = 0.0,
+                 erase_scale: Sequence[float] = (0.02, 0.33), erase_ratio: Sequence[float] = (0.3, 3.3)):
         from .._native import C
 
         self._C = C
@@ -310,6 +324,42 @@ class DeviceLoader:
         self.nhwc = bool(channels_last)
         self.seed = int(seed)
         self.epoch = 0
+        self.training = True
+        self.resize = None if resize is None else int(resize)
+        if self.resize is not None:
+            self._init_resize(crop_scale, crop_ratio, erase_prob, erase_scale, erase_ratio)
+
+    def _init_resize(self, crop_scale, crop_ratio, erase_prob, erase_scale, erase_ratio) -> None:
+        from ..ops.resize_crop import _range, whole_image_record
+
+        if self.pad:
+            raise ValueError("DeviceLoader: crop_padding (RandomCrop) and resize (RandomResizedCrop) exclude each other")
+        if self.out_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"DeviceLoader: resize writes float32 or bfloat16 images, got {self.out_dtype}")
+        H, W = int(self.x.shape[1]), int(self.x.shape[2])
+        channels = int(self.x.shape[3]) if self.x.dim() == 4 else 1
+        if self.x.dim() not in (3, 4) or H * W * channels > 32 * 1024:
+            raise ValueError(f"DeviceLoader: resize takes images [N, H, W] or [N, H, W, C] of at most 32 KiB each, "
+                             f"got {tuple(self.x.shape)}")
+        if not 1 <= self.resize <= 1024:
+            raise ValueError(f"DeviceLoader: resize must be in [1, 1024], got {self.resize}")
+        if not 0.0 <= float(erase_prob) <= 1.0:
+            raise ValueError(f"DeviceLoader: erase_prob must be in [0, 1], got {erase_prob}")
+        self.crop_scale = None if crop_scale is None else _range(crop_scale, "DeviceLoader crop_scale")
+        self.draw_cfg = (_range(crop_ratio, "DeviceLoader crop_ratio"), self.hflip, float(erase_prob),
+                         _range(erase_scale, "DeviceLoader erase_scale"),
+                         _range(erase_ratio, "DeviceLoader erase_ratio"))
+        self.eval_rec = whole_image_record(H, W, self.device)
+
+    def train(self, mode: bool = True) -> "DeviceLoader":
+        """Augmentation on (``resize``: a crop, flip and erase drawn per sample)."""
+        self.training = bool(mode)
+        return self
+
+    def eval(self) -> "DeviceLoader":
+        """The evaluation transform of ``resize``: the whole image resized, nothing drawn (one launch a batch).
+        Without ``resize`` the loader is unchanged."""
+        return self.train(False)
 
     def set_epoch(self, epoch: int) -> None:
         self.epoch = int(epoch)
@@ -327,6 +377,16 @@ class DeviceLoader:
 
     def batch(self, idx: torch.Tensor, step_seed: int):
         """(images, labels) for an explicit device index tensor."""
+        if self.resize is not None:
+            rec = self.eval_rec
+            if self.training:
+                from ..random import Draw
+
+                H, W = int(self.x.shape[1]), int(self.x.shape[2])
+                rec = self._C.crop_draw(Draw(self.device).snapshot, int(idx.shape[0]), H, W, self.resize,
+                                        self.crop_scale, *self.draw_cfg)
+            return self._C.resize_crop(self.x, self.y, idx, rec, self.resize, self.mean, self.std, self.nhwc,
+                                       self.out_dtype)
         return self._C.gather_augment(self.x, self.y, idx, self.pad, self.hflip, self.mean, self.std,
                                       step_seed, self.nhwc, self.out_dtype)
 

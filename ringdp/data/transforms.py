@@ -103,6 +103,79 @@ class RandomHorizontalFlip:
         return f"RandomHorizontalFlip(p={self.p})"
 
 
+def _resize_u8(img: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
+    """uint8 HW[C] -> uint8 size[C]: plain bilinear (half-pixel centres, no antialiasing), rounded to nearest."""
+    if img.dtype != torch.uint8:
+        raise TypeError("resize expects a uint8 image")
+    t = _hwc(img).permute(2, 0, 1).unsqueeze(0).to(torch.float32)
+    t = torch.nn.functional.interpolate(t, size=size, mode="bilinear", align_corners=False, antialias=False)
+    out = t.round_().clamp_(0, 255).to(torch.uint8)[0].permute(1, 2, 0)
+    return out.squeeze(-1) if img.dim() == 2 else out.contiguous()
+
+
+def _size2(size) -> Tuple[int, int]:
+    size = (size, size) if isinstance(size, int) else tuple(int(s) for s in size)
+    if len(size) != 2 or min(size) < 1:
+        raise ValueError(f"size must be a positive int or a pair of them, got {size}")
+    return size
+
+
+class Resize:
+    """Bilinear resize of a uint8 HW[C] image to ``size`` (an int means ``size x size``), the definition the device
+    loader's ``resize`` uses (``ringdp.ops.resize_crop``); the result is rounded back to uint8 for ``ToTensor``."""
+
+    def __init__(self, size):
+        self.size = _size2(size)
+
+    def __call__(self, img: torch.Tensor) -> torch.Tensor:
+        return _resize_u8(img, self.size)
+
+    def __repr__(self) -> str:
+        return f"Resize(size={self.size})"
+
+
+class RandomResizedCrop:
+    """torchvision's ``RandomResizedCrop`` on a uint8 HW[C] image: ten attempts at a box of ``scale`` x the area
+    and a log-uniform ``ratio``, else the centre crop with the ratio clamped; the box is resized like ``Resize``."""
+
+    def __init__(self, size, scale: Sequence[float] = (0.08, 1.0), ratio: Sequence[float] = (3 / 4, 4 / 3),
+                 generator: Optional[torch.Generator] = None):
+        self.size = _size2(size)
+        self.scale = tuple(float(s) for s in scale)
+        self.ratio = tuple(float(r) for r in ratio)
+        if not 0 < self.scale[0] <= self.scale[1] or not 0 < self.ratio[0] <= self.ratio[1]:
+            raise ValueError(f"RandomResizedCrop: expected 0 < lo <= hi, got scale {self.scale}, ratio {self.ratio}")
+        self.generator = generator
+
+    def get_params(self, H: int, W: int) -> Tuple[int, int, int, int]:
+        """The box ``(y0, x0, h, w)`` for an ``H x W`` image."""
+        import math
+
+        lr0, lr1 = math.log(self.ratio[0]), math.log(self.ratio[1])
+        for _ in range(10):
+            u = torch.rand(2, generator=self.generator).tolist()
+            area = H * W * (self.scale[0] + (self.scale[1] - self.scale[0]) * u[0])
+            ar = math.exp(lr0 + (lr1 - lr0) * u[1])
+            w, h = int(round(math.sqrt(area * ar))), int(round(math.sqrt(area / ar)))
+            if 1 <= w <= W and 1 <= h <= H:
+                y0 = int(torch.randint(0, H - h + 1, (1,), generator=self.generator))
+                x0 = int(torch.randint(0, W - w + 1, (1,), generator=self.generator))
+                return y0, x0, h, w
+        h, w = H, W
+        if W / H < self.ratio[0]:
+            h = min(max(int(round(W / self.ratio[0])), 1), H)
+        elif W / H > self.ratio[1]:
+            w = min(max(int(round(H * self.ratio[1])), 1), W)
+        return (H - h) // 2, (W - w) // 2, h, w
+
+    def __call__(self, img: torch.Tensor) -> torch.Tensor:
+        y0, x0, h, w = self.get_params(img.shape[0], img.shape[1])
+        return _resize_u8(img[y0:y0 + h, x0:x0 + w], self.size)
+
+    def __repr__(self) -> str:
+        return f"RandomResizedCrop(size={self.size}, scale={self.scale}, ratio={self.ratio})"
+
+
 def default_collate(batch: List[Tuple[object, object]]):
     """Stack (image, target) pairs into (images, targets) tensors."""
     xs, ys = zip(*batch)
