@@ -678,6 +678,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("N"), py::arg("K"), py::arg("out_bf16") = true, py::arg("bias") = py::none(), py::arg("act") = 0,
         py::arg("residual") = py::none(), py::arg("preact") = py::none());
   m.def("gemm_fp8_splitk_f32", &ops::gemm_fp8_splitk_f32);
+  m.def("mx_quantize", &ops::mx_quantize, py::arg("x"), py::arg("rowwise"), py::arg("colwise"),
+        "MXFP8 (e4m3 + E8M0 per block of 32) of a bf16 / fp32 matrix: (q, s, qt, st), the orientation not asked for None");
+  m.def("mx_quantize_weights", &ops::mx_quantize_weights,
+        "MXFP8 copies, both orientations, of many fp32 weights in one launch: flat (q, s, qt, st) per weight");
+  m.def("gemm_mxfp8", &ops::gemm_mxfp8, py::arg("a"), py::arg("sa"), py::arg("b"), py::arg("sb"), py::arg("M"),
+        py::arg("N"), py::arg("K"), py::arg("out_bf16") = true, py::arg("bias") = py::none(), py::arg("act") = 0,
+        py::arg("residual") = py::none(), py::arg("preact") = py::none());
+  m.def("gemm_mxfp8_splitk_f32", &ops::gemm_mxfp8_splitk_f32);
   m.def("set_bf16_tile_mode", &ops::set_bf16_tile_mode, "0 auto, 128 / 256: force the bf16 GEMM tile kernel");
   m.def("set_gemm256_phased", &kern::set_gemm256_phased, "K-contiguous 256x256 GEMM: 1 phased pipeline, 0 older kernel");
   m.def("set_gemm_two_wg", &kern::set_gemm_two_wg, "bf16 K-contiguous GEMMs on the 2-workgroup 256x128 kernel: 0 never (default), 1 always, 2 N <= 1024; group_m > 0 sets its tile-order group",

@@ -482,6 +482,32 @@ struct QuantTTable {
   QuantTEntry e[kQuantTMax];
 };
 void fp8_quantize_multi(const QuantTTable& t, hipStream_t s);  // one site: hist[0] <- max hist[1 .. 1+n) when > 0
+// MXFP8 (mxfp8.hip): e4m3 elements with one E8M0 scale byte per block of 32, no state between calls.
+// x [rows][cols] bf16 (or fp32, rounded to bf16 on load), cols % 32 == 0, 16-B aligned.  Row-wise: q [rows][Cp],
+// s [rows][Cp/32]; column-wise, stored transposed: qt [cols][Rp], st [cols][Rp/32]; Cp / Rp = mx_pad(cols / rows)
+// (padding: zero elements, scale byte 127).  A null q or qt skips that orientation.
+int64_t mx_pad(int64_t n);  // n rounded up to 128
+int64_t mx_quant_tiles(int64_t rows, int64_t cols);
+void mx_quantize(const void* x, bool x_f32, int64_t rows, int64_t cols, uint8_t* q, uint8_t* s, uint8_t* qt,
+                 uint8_t* st, hipStream_t stream);
+struct MxQuantEntry {
+  const float* src;  // [rows][cols] fp32
+  int64_t rows, cols;
+  uint8_t *q, *s, *qt, *st;
+  int tile0;
+};
+constexpr int kMxQuantMax = 60;  // 60 x 64 B + header < the 4 KiB kernel-argument limit
+struct MxQuantTable {
+  int n;
+  int total_tiles;
+  MxQuantEntry e[kMxQuantMax];
+};
+void mx_quantize_multi(const MxQuantTable& t, hipStream_t stream);
+// MXFP8 GEMM (gemm_mxfp8_256.hip): A [M][Kbytes], B [N][Kbytes] e4m3, sa [M][Kbytes/32], sb [N][Kbytes/32] E8M0,
+// Kbytes % 128 == 0, N % 4 == 0; ep as gemm_fp8's without scale_a/b, q8 and stats.  Returns the number of
+// k-splits launched (kSplitK: that many [M][N] planes of ep.partial were written).
+int gemm_mxfp8_256(const uint8_t* A, const uint8_t* sa, const uint8_t* B, const uint8_t* sb, int M, int N, int Kbytes,
+                   const GemmEpilogue& ep, int splits, hipStream_t s);
 // column sums of a bf16 [rows][cols] matrix as colsum_parts(rows) fp32 partial rows (sum them with splitk_sum;
 // fp8_quantize_delayed's colsum_part has one partial row per 64-row tile instead)
 int colsum_parts(int64_t rows);

@@ -147,6 +147,16 @@ void set_bf16_tile_mode(int64_t mode);
 void set_fp8_tile_mode(int64_t mode);
 void gemm_fp8_splitk_f32(const at::Tensor& a, const at::Tensor& b, const at::Tensor& scale_a,
                          const at::Tensor& scale_b, int64_t M, int64_t N, int64_t K, int64_t splits, at::Tensor out);
+// MXFP8 (mxfp8_ops.cpp): e4m3 with one E8M0 scale per block of 32.  mx_quantize -> (q [R][Cp], s [R][Cp/32],
+// qt [C][Rp], st [C][Rp/32]) with the orientation not asked for as None; Cp / Rp round up to 128
+std::tuple<c10::optional<at::Tensor>, c10::optional<at::Tensor>, c10::optional<at::Tensor>, c10::optional<at::Tensor>>
+mx_quantize(const at::Tensor& x, bool rowwise, bool colwise);
+std::vector<at::Tensor> mx_quantize_weights(const std::vector<at::Tensor>& ws);  // fp32 weights -> flat (q, s, qt, st)...
+at::Tensor gemm_mxfp8(const at::Tensor& a, const at::Tensor& sa, const at::Tensor& b, const at::Tensor& sb, int64_t M,
+                      int64_t N, int64_t K, bool out_bf16, const c10::optional<at::Tensor>& bias, int64_t act,
+                      const c10::optional<at::Tensor>& residual, const c10::optional<at::Tensor>& preact);
+void gemm_mxfp8_splitk_f32(const at::Tensor& a, const at::Tensor& sa, const at::Tensor& b, const at::Tensor& sb,
+                           int64_t M, int64_t N, int64_t K, int64_t splits, at::Tensor out);
 
 }  // namespace ops
 }  // namespace ringdp

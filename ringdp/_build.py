@@ -36,9 +36,12 @@ EXT_NAME = "_C"
 ARCH = os.environ.get("RINGDP_ARCH", "gfx950")
 ROCM = Path(os.environ.get("ROCM_PATH", "/opt/rocm"))
 # Extra hipcc flags of single units.  resize_crop.hip: plain fp32 interpolation arithmetic, kept on the scalar
-# v_fma_f32 / v_mul_f32 forms (no packed fp32 pairs).
+# v_fma_f32 / v_mul_f32 forms (no packed fp32 pairs); the MXFP8 units likewise.
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 UNIT_FLAGS = {
-    "resize_crop.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "resize_crop.hip": _NO_PK_F32,
+    "mxfp8.hip": _NO_PK_F32,
+    "gemm_mxfp8_256.hip": _NO_PK_F32,
 }
 
 

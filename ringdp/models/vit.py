@@ -110,7 +110,8 @@ class EncoderBlock(nn.Module):
             o = AttentionF.apply(qkv, B, T, self.num_heads)
             x = linear(o, att.out_proj, residual=x)
             h, x = layernorm_fork(x, self.ln_2, fc1.weight)
-            if fp8_mlp_fusable(h.shape[0], h.shape[1], fc1.weight.shape[0]):  # e4m3 from the GEMM epilogues
+            # per-tensor recipe: e4m3 from the GEMM epilogues; the MXFP8 recipe runs the plain linears below
+            if fp8_mlp_fusable(h.shape[0], h.shape[1], fc1.weight.shape[0]):
                 return MLPF8.apply(h, fc1.weight, fc1.bias, fc2.weight, fc2.bias, x)
             h = linear(h, fc1, act=2)
             return linear(h, fc2, residual=x)

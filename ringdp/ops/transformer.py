@@ -26,17 +26,31 @@ _ATTN_BWD_GEMMS = os.environ.get("RINGDP_ATTN_BWD_GEMMS", "0") == "1"  # dS kern
 _ATTN_RECOMPUTE = os.environ.get("RINGDP_ATTN_RECOMPUTE", "1") == "1"
 # LayerNorm backward also emits the column sums of dx (the producing linear's bias gradient)
 _LN_COLSUM = os.environ.get("RINGDP_LN_COLSUM", "0") == "1"
-_FP8 = {"on": False}
+_FP8 = {"on": False, "mx": False}
+_FP8_RECIPES = ("tensor", "mx")
 
 
-def set_fp8(on: bool = True) -> None:
+def set_fp8(on: bool = True, recipe: Optional[str] = None) -> None:
     """Run the linear layers' forward, data-gradient and weight-gradient GEMMs in e4m3 on the
-    block-scaled MFMA (per-tensor current scaling; attention products stay bf16)."""
+    block-scaled MFMA (attention products stay bf16).  ``recipe``: ``"tensor"`` - one delayed scale per
+    tensor (the default); ``"mx"`` - MXFP8, one E8M0 scale per block of 32 computed in the quantising pass, no
+    state between calls.  ``None`` reads ``RINGDP_FP8_RECIPE`` (default ``tensor``).  Turning fp8 off
+    returns to the default recipe."""
+    if recipe is None:
+        recipe = os.environ.get("RINGDP_FP8_RECIPE", "") or "tensor"
+    if recipe not in _FP8_RECIPES:
+        raise ValueError(f"set_fp8: unknown recipe {recipe!r} (expected one of {_FP8_RECIPES})")
     _FP8["on"] = bool(on)
+    _FP8["mx"] = bool(on) and recipe == "mx"
 
 
 def fp8_enabled() -> bool:
     return _FP8["on"]
+
+
+def fp8_recipe() -> str:
+    """The recipe fp8 linears run (``"tensor"`` while fp8 is off)."""
+    return "mx" if _FP8["mx"] else "tensor"
 
 
 # {id(weight): bf16 copy} for the forward in progress (VisionTransformer.forward_rows casts every linear
@@ -55,7 +69,15 @@ def cast_weights(ws) -> None:
     progress (see _bf16 / _bf16_t): the backward's data-gradient GEMMs take W^T K-contiguous."""
     ws = [w for w in ws if w.is_cuda and w.dtype == torch.float32 and w.dim() == 2]
     _BF16_WEIGHTS_T.clear()  # the previous step's backward has taken what it needed
-    if ws and _FP8["on"]:
+    if ws and _FP8["mx"]:
+        # MXFP8: both orientations of every eligible weight from one launch; the rest take the bf16 path below
+        mx = [w for w in ws if _mx_ok(w.shape[1], w.shape[0])]
+        ws = [w for w in ws if not _mx_ok(w.shape[1], w.shape[0])]
+        if mx:
+            flat = C.mx_quantize_weights([w.detach().contiguous() for w in mx])
+            for i, w in enumerate(mx):
+                _MX_WEIGHTS[id(w)] = (w, tuple(flat[4 * i:4 * i + 4]))
+    elif ws and _FP8["on"]:
         if _FP8_WQ_BATCH and _FP8_DELAYED and _fp8_weights_batched(ws):
             return
         # fp8 linears quantise W / W^T themselves: plain casts only
@@ -73,6 +95,24 @@ def cast_weights(ws) -> None:
 def clear_weights() -> None:
     _BF16_WEIGHTS.clear()
     _FP8_WEIGHTS.clear()
+    _MX_WEIGHTS.clear()
+
+
+_MX_WEIGHTS: dict = {}  # {id(weight): (weight, (q, s, qt, st))} for the forward in progress (MXFP8)
+
+
+def _mx_ok(K: int, N: int) -> bool:
+    """MXFP8 linears need whole 32-blocks along both of the weight's axes."""
+    return K % 32 == 0 and N % 32 == 0
+
+
+def _mx_weight(w: torch.Tensor):
+    """(q, s, qt, st) of a linear weight [N, K]: row-wise (blocks along K, the forward GEMM's reduction) and
+    column-wise (W^T [K, Np], blocks along N, the data-gradient GEMM's reduction)."""
+    e = _MX_WEIGHTS.get(id(w))
+    if e is not None and e[0] is w:
+        return e[1]
+    return C.mx_quantize(w.detach().contiguous(), True, True)
 
 
 # fp8: every linear weight's e4m3 copies (q, q^T, scale) from one launch per forward (cast_weights), instead of a
@@ -139,7 +179,11 @@ class LinearF(torch.autograd.Function):
     def forward(ctx, x, w, b, residual, act: int, out_f32: bool):
         M, K = x.shape
         N = w.shape[0]
-        if _FP8["on"] and M % 16 == 0 and N % 16 == 0 and K % 16 == 0:
+        ctx.mx = False
+        if _FP8["mx"]:
+            if _mx_ok(K, N):
+                return _linear_mx_fwd(ctx, x, w, b, residual, act, out_f32)
+        elif _FP8["on"] and M % 16 == 0 and N % 16 == 0 and K % 16 == 0:
             return _linear_fp8_fwd(ctx, x, w, b, residual, act, out_f32)
         ctx.fp8 = False
         if getattr(x, "_ringdp_q8", None) is not None:
@@ -164,6 +208,8 @@ class LinearF(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
+        if ctx.mx:
+            return _linear_mx_bwd(ctx, dy)
         if ctx.fp8:
             return _linear_fp8_bwd(ctx, dy)
         x, wb, pre = ctx.saved_tensors
@@ -305,8 +351,9 @@ _FP8_MLP_FUSED = os.environ.get("RINGDP_FP8_MLP_FUSED", "1") == "1"
 
 
 def fp8_mlp_fusable(M: int, D: int, Hd: int) -> bool:
-    """MLPF8 needs whole 16-row / 16-column e4m3 pieces and whole 128-byte k-steps (K = D)."""
-    return _FP8_MLP_FUSED and _FP8_DELAYED and M % 16 == 0 and Hd % 16 == 0 and D % 128 == 0
+    """MLPF8 needs whole 16-row / 16-column e4m3 pieces and whole 128-byte k-steps (K = D); it is a per-tensor
+    construct (never with the MXFP8 recipe)."""
+    return not _FP8["mx"] and _FP8_MLP_FUSED and _FP8_DELAYED and M % 16 == 0 and Hd % 16 == 0 and D % 128 == 0
 
 
 def _epilogue_site(w, slot, M, N, device, exact_from: int):
@@ -415,6 +462,47 @@ def _linear_fp8_bwd(ctx, dy):
         dw = grad_buffer(w)
         C.gemm_fp8_splitk_f32(dztq, xtq, sdz, sx, N, K, M, _splits(M, N, K), dw)
     if want_db and db is None:
+        db = grad_buffer(b)
+        C.colsum_f32(dz, db)
+    dres = dyb if has_res and ctx.needs_input_grad[3] else None
+    return dx, dw, db, dres, None, None
+
+
+def _linear_mx_fwd(ctx, x, w, b, residual, act, out_f32):
+    """MXFP8 linear: every GEMM operand is blocked along that GEMM's own reduction axis, so x and W are
+    quantised in both orientations (one launch each; the weights' comes from cast_weights)."""
+    M, K = x.shape
+    N = w.shape[0]
+    want_dw = ctx.needs_input_grad[1]
+    xq, xs, xqt, xst = C.mx_quantize(x.contiguous(), True, want_dw)  # blocks along K; along M for dW
+    wq, ws, wqt, wst = _mx_weight(w)                                  # blocks along K; along N for dx
+    pre = torch.empty(M, N, device=x.device, dtype=torch.bfloat16) if act == 2 else None
+    y = C.gemm_mxfp8(xq, xs, wq, ws, M, N, xq.shape[1], not out_f32, b, act, residual, pre)
+    ctx.mx = True
+    ctx.save_for_backward(xqt, xst, wqt, wst, pre)
+    ctx.shape = (M, K)
+    ctx.params = (w, b)
+    ctx.cfg = (act, residual is not None, N)
+    return y
+
+
+def _linear_mx_bwd(ctx, dy):
+    xqt, xst, wqt, wst, pre = ctx.saved_tensors
+    w, b = ctx.params
+    act, has_res, N = ctx.cfg
+    M, K = ctx.shape
+    dyb = dy.contiguous() if dy.dtype == torch.bfloat16 else _bf16(dy)
+    dz = C.gelu_bwd(dyb, pre) if act == 2 else dyb
+    want_dx, want_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    dx = dw = db = None
+    if want_dx or want_dw:
+        dzq, dzs, dzqt, dzst = C.mx_quantize(dz, want_dx, want_dw)  # blocks along N for dx, along M for dW
+    if want_dx:  # dx[m][k] = sum_n dz[m][n] W[n][k]: W column-wise, i.e. W^T blocked along n
+        dx = C.gemm_mxfp8(dzq, dzs, wqt, wst, M, K, dzq.shape[1], True)
+    if want_dw:  # dW[n][k] = sum_m dz[m][n] x[m][k]: both column-wise, blocked along m
+        dw = grad_buffer(w)
+        C.gemm_mxfp8_splitk_f32(dzqt, dzst, xqt, xst, N, K, dzqt.shape[1], _splits(M, N, K), dw)
+    if b is not None and ctx.needs_input_grad[2]:
         db = grad_buffer(b)
         C.colsum_f32(dz, db)
     dres = dyb if has_res and ctx.needs_input_grad[3] else None
@@ -543,8 +631,10 @@ class LayerNormFork8(torch.autograd.Function):
 def _fork8_ok(x, consumer_w) -> bool:
     """LayerNormFork8's placeholder ``y`` is only valid if the consumer takes the fp8 path: LinearF's
     condition (rows, D and the consumer's out_features multiples of 16) and the e4m3 LayerNorm kernel's
-    D <= 2048."""
+    D <= 2048.  Never with the MXFP8 recipe (its linears quantise their own inputs)."""
     rows, d = x.shape[0], x.shape[-1]
+    if _FP8["mx"]:
+        return False
     return x.dim() == 2 and rows % 16 == 0 and d % 16 == 0 and d <= 2048 and consumer_w.shape[0] % 16 == 0 \
         and consumer_w.shape[-1] == d
 

@@ -1,0 +1,107 @@
+"""MXFP8 kernels against their per-tensor counterparts on one GPU.
+
+GEMM: ``gemm_mxfp8`` vs ``gemm_fp8`` (bf16 output, no epilogue extras) on the ViT-B/16 linear shapes at the
+benchmark batch (tokens = 128 x 197) and at 8192^3, as TF/s from 2 M N K over device-event time.
+Quantiser: ``mx_quantize`` (both orientations) vs ``fp8_quantize_both_delayed`` on the [tokens, 768] and
+[tokens, 3072] activations, as GB/s of the bytes each must move (one bf16 read, two e4m3 writes, plus MX scales).
+The two variants of a row are timed alternately, ``--rounds`` windows each; the median and the spread are printed.
+One JSON line per row.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from ringdp._native import C  # noqa: E402
+
+
+def _time(fn, iters: int) -> float:
+    """Milliseconds per call over ``iters`` calls between two device events."""
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def _pair(f_mx, f_pt, iters: int, rounds: int):
+    for f in (f_mx, f_pt):  # warm-up: code objects, allocator
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    t_mx, t_pt = [], []
+    for _ in range(rounds):
+        t_mx.append(_time(f_mx, iters))
+        t_pt.append(_time(f_pt, iters))
+    return t_mx, t_pt
+
+
+def _stats(ts):
+    return statistics.median(ts), min(ts), max(ts)
+
+
+def bench_gemm(M: int, N: int, K: int, splits: int, iters: int, rounds: int) -> dict:
+    a = torch.randn(M, K, device="cuda").bfloat16()
+    b = torch.randn(N, K, device="cuda").bfloat16()
+    aq, sa, _, _ = C.mx_quantize(a, True, False)
+    bq, sb, _, _ = C.mx_quantize(b, True, False)
+    pa, _, psa = C.fp8_quantize_both(a)
+    pb, _, psb = C.fp8_quantize_both(b)
+    Kp = aq.shape[1]
+    if splits > 1:  # a weight gradient: split-K into fp32
+        out = torch.empty(M, N, device="cuda")
+        t_mx, t_pt = _pair(lambda: C.gemm_mxfp8_splitk_f32(aq, sa, bq, sb, M, N, Kp, splits, out),
+                           lambda: C.gemm_fp8_splitk_f32(pa, pb, psa, psb, M, N, K, splits, out), iters, rounds)
+    else:
+        t_mx, t_pt = _pair(lambda: C.gemm_mxfp8(aq, sa, bq, sb, M, N, Kp, True),
+                           lambda: C.gemm_fp8(pa, pb, psa, psb, M, N, K, True), iters, rounds)
+    flop = 2.0 * M * N * K
+    (m, lo, hi), (p, plo, phi) = _stats(t_mx), _stats(t_pt)
+    return {"kind": "gemm", "M": M, "N": N, "K": K, "splits": splits, "mx_ms": round(m, 4), "mx_ms_range": [round(lo, 4), round(hi, 4)],
+            "tensor_ms": round(p, 4), "tensor_ms_range": [round(plo, 4), round(phi, 4)],
+            "mx_tflops": round(flop / m / 1e9, 1), "tensor_tflops": round(flop / p / 1e9, 1)}
+
+
+def bench_quant(R: int, Cc: int, iters: int, rounds: int) -> dict:
+    x = torch.randn(R, Cc, device="cuda").bfloat16()
+    hist = torch.zeros(1 + C.fp8_delayed_slots(R, Cc), device="cuda")
+    C.fp8_quantize_both_delayed(x, hist, True)  # the site's first call measures the amax
+    t_mx, t_pt = _pair(lambda: C.mx_quantize(x, True, True),
+                       lambda: C.fp8_quantize_both_delayed(x, hist, False, roll=False), iters, rounds)
+    byt = R * Cc * (2 + 2)
+    (m, lo, hi), (p, plo, phi) = _stats(t_mx), _stats(t_pt)
+    return {"kind": "quant", "R": R, "C": Cc, "mx_ms": round(m, 4), "mx_ms_range": [round(lo, 4), round(hi, 4)],
+            "tensor_ms": round(p, 4), "tensor_ms_range": [round(plo, 4), round(phi, 4)],
+            "mx_gbs": round((byt + 2 * R * Cc / 32) / m / 1e6, 1), "tensor_gbs": round(byt / p / 1e6, 1)}
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--batch", type=int, default=128, help="images per step (197 tokens each)")
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=5)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("mxfp8_bench: needs a GPU")
+    T = args.batch * 197
+    # forward / data-gradient shapes of qkv, proj, fc1, fc2; two weight gradients (split-K over the tokens, the
+    # count LinearF asks for); 8192^3
+    Tk = T // 128 * 128
+    shapes = [(T, 2304, 768, 1), (T, 768, 768, 1), (T, 3072, 768, 1), (T, 768, 3072, 1), (T, 768, 2304, 1),
+              (3072, 768, Tk, 4), (768, 3072, Tk, 4), (8192, 8192, 8192, 1)]
+    for M, N, K, splits in shapes:
+        print(json.dumps(bench_gemm(M, N, K, splits, args.iters, args.rounds)), flush=True)
+    for R, Cc in ((T, 768), (T, 3072)):
+        print(json.dumps(bench_quant(R, Cc, args.iters, args.rounds)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
