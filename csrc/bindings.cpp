@@ -685,6 +685,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_mxfp8", &ops::gemm_mxfp8, py::arg("a"), py::arg("sa"), py::arg("b"), py::arg("sb"), py::arg("M"),
         py::arg("N"), py::arg("K"), py::arg("out_bf16") = true, py::arg("bias") = py::none(), py::arg("act") = 0,
         py::arg("residual") = py::none(), py::arg("preact") = py::none());
+  m.def("gemm_mxfp8_quant_out", &ops::gemm_mxfp8_quant_out, py::arg("a"), py::arg("sa"), py::arg("b"), py::arg("sb"),
+        py::arg("M"), py::arg("N"), py::arg("K"), py::arg("bias") = py::none(), py::arg("act") = 0,
+        py::arg("preact") = py::none(), py::arg("colsum") = py::none(),
+        "gemm_mxfp8 with MXFP8 outputs (q, s, qt, st) written by the GEMM epilogue: act 0, 2 (GELU, writes preact) or "
+        "3 (GELU backward, reads preact); colsum <- column sums of the bf16-rounded values");
   m.def("gemm_mxfp8_splitk_f32", &ops::gemm_mxfp8_splitk_f32);
   m.def("set_bf16_tile_mode", &ops::set_bf16_tile_mode, "0 auto, 128 / 256: force the bf16 GEMM tile kernel");
   m.def("set_gemm256_phased", &kern::set_gemm256_phased, "K-contiguous 256x256 GEMM: 1 phased pipeline, 0 older kernel");

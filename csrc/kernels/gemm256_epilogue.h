@@ -8,6 +8,7 @@
 
 #include "device_common.h"
 #include "kernels.h"
+#include "mx_device.h"
 
 namespace ringdp {
 namespace kern {
@@ -246,6 +247,164 @@ __device__ __forceinline__ void gemm256_store_q8(const dev::f32x4 (&acc)[8][4], 
       }
     }
   }
+}
+
+// MXFP8 outputs, gemm256_store_mx (GemmEpilogue::mx_q / mx_s / mx_qt / mx_st; acc[i][j] covers rows mrow + 16 i,
+// columns ncol + 16 j): the bytes mx_quantize (mxfp8.hip) would make of the bf16 C this epilogue would have stored, both
+// orientations, without that C ever reaching memory.
+//   1. The wave's 128 x 64 final values, rounded to bf16 once and forced to 0 past the M / N edge, go to LDS as
+//      [128 rows][128 B], 16-B chunk c of row r at c ^ (r & 7) (side loads staged by halves, as the q8 path).
+//   2. Row-wise: the tile holds 128 rows x 2 blocks of 32 columns; lane l takes block l & 1 of row 32 p + l / 2
+//      in pass p: four 16-B reads (8 consecutive lanes hit 8 distinct chunks), amax in-lane, two 16-B stores.
+//      Lanes l and l ^ 1 hold the two scales of a row's 64 columns: the even one stores both as one 16-bit word.
+//   3. Column-wise: lane l owns column l and walks it down the rows, 32 at a time: the 64 lanes of one read
+//      cover the 128 bytes of one LDS row (the swizzle permutes chunks inside the row: no bank conflict); amax
+//      and the column sum in-lane, two 16-B stores per block, the four scale bytes of the 128 rows as one dword.
+// Padding comes out on its own: columns in [N, Np) and rows in [M, Mp) are zeros in the LDS image, i.e. zero
+// bytes with scale 127; Np % 128 == 0 against 64-column wave tiles and Mp % 128 == 0 against 128-row ones, so a
+// block or a wave tile is wholly inside or outside the padded shape.  One writer per byte, no atomics.
+// Each wave reads back only what it wrote (LDS executes one wave's operations in order): no barrier.
+// Step 1 is specialised per activation; steps 2 and 3 exist once and handle one pass / block at a time (all
+// four blocks' reads hoisted above the first stores spilled 55 registers).
+template <int ACT>
+__device__ __forceinline__ void gemm256_mx_to_lds(const dev::f32x4 (&acc)[8][4], const GemmEpilogue& ep,
+                                                  const EpiFlags& fl, int M, int N, int mrow, int ncol, float sa,
+                                                  char* lds_wave) {  // step 1
+  using namespace ringdp::dev;
+  const int lane = threadIdx.x & 63, fr = lane & 15, fq = lane >> 4;
+  f32x4 bias[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int n = ncol + 16 * j;
+    bias[j] = (fl.bias && n < N) ? *reinterpret_cast<const f32x4*>(ep.bias + n) : zero_f32x4();
+  }
+  const bool has_side = fl.res || ACT == 3;
+  const bf16* side = static_cast<const bf16*>(fl.res ? ep.residual : ep.preact);
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    bf16x4 sv[4][4];
+#pragma unroll
+    for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        sv[ii][j] = bf16x4{(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
+        if (has_side) {
+          const int m = min(mrow + 16 * (4 * half + ii), M - 1), n = min(ncol + 16 * j, N - 4);
+          sv[ii][j] = *reinterpret_cast<const bf16x4*>(side + (int64_t)m * ep.ldc + n);
+        }
+      }
+#pragma unroll
+    for (int ii = 0; ii < 4; ++ii) {
+      const int i = 4 * half + ii;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int m = mrow + 16 * i, n = ncol + 16 * j;
+        const bool ok = m < M && n < N;
+        float v[4];
+        epi_values<ACT>(acc[i][j], sa, bias[j], sv[ii][j], fl.res, v);
+        if (fl.st_pre && ok)
+          *reinterpret_cast<bf16x4*>(static_cast<bf16*>(ep.preact) + (int64_t)m * ep.ldc + n) =
+              bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
+        epi_finish<ACT>(v, sv[ii][j], fl.res);
+        const bf16 z = (bf16)0.f;  // rows past M hold clamped-row garbage
+        const int r = 16 * i + fr, c = 16 * j + 4 * fq;
+        *reinterpret_cast<bf16x4*>(lds_wave + r * 128 + ((((c >> 3) ^ (r & 7)) << 4) | ((c & 7) << 1))) =
+            bf16x4{ok ? (bf16)v[0] : z, ok ? (bf16)v[1] : z, ok ? (bf16)v[2] : z, ok ? (bf16)v[3] : z};
+      }
+    }
+  }
+}
+
+// steps 2 and 3 of gemm256_store_mx: the wave's LDS image -> MXFP8 in both orientations, and the column sums
+__device__ __forceinline__ void gemm256_mx_from_lds(const GemmEpilogue& ep, int M, int N, int mrow, int ncol,
+                                                    const char* lds_wave) {
+  const int lane = threadIdx.x & 63, fr = lane & 15, fq = lane >> 4;
+  // the wave tile's first row / column (wave-uniform: the branches on them are scalar)
+  const int m_base = __builtin_amdgcn_readfirstlane(mrow - fr), n_base = __builtin_amdgcn_readfirstlane(ncol - 4 * fq);
+  const int Np = (N + 127) / 128 * 128, Mp = (M + 127) / 128 * 128;
+  auto lo = [](unsigned w) { return __uint_as_float(w << 16); };  // the two bf16 of a dword as floats
+  auto hi = [](unsigned w) { return __uint_as_float(w & 0xffff0000u); };
+  if (n_base < Np) {  // ---- row-wise
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const int r = 32 * p + (lane >> 1), blk = lane & 1;
+      float f[32];
+      float a = 0.f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const uint4 w = *reinterpret_cast<const uint4*>(lds_wave + r * 128 + (((4 * blk + k) ^ (r & 7)) << 4));
+        const unsigned u[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          f[8 * k + 2 * t] = lo(u[t]);
+          f[8 * k + 2 * t + 1] = hi(u[t]);
+          a = fmaxf(a, fmaxf(fabsf(f[8 * k + 2 * t]), fabsf(f[8 * k + 2 * t + 1])));
+        }
+      }
+      const int e = mx_exp(a);
+      unsigned w[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) w[k] = mx_pack4(f[4 * k], f[4 * k + 1], f[4 * k + 2], f[4 * k + 3], e);
+      const unsigned sb = (unsigned)(e + 127);
+      const unsigned s2 = sb | ((unsigned)__shfl_xor((int)sb, 1, 64) << 8);  // (even lanes: blocks 0 and 1 of the row)
+      const int m = m_base + r;
+      if (m < M) {
+        uint8_t* dst = ep.mx_q + (int64_t)m * Np + n_base + 32 * blk;
+        *reinterpret_cast<uint4*>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
+        *reinterpret_cast<uint4*>(dst + 16) = make_uint4(w[4], w[5], w[6], w[7]);
+        if (blk == 0)
+          *reinterpret_cast<unsigned short*>(ep.mx_s + (int64_t)m * (Np / 32) + (n_base >> 5)) = (unsigned short)s2;
+      }
+      asm volatile("" ::: "memory");  // one pass's 32 values live at a time: the next pass's reads stay below
+    }
+  }
+  if (m_base < Mp) {  // ---- column-wise (and the column sums: this lane walks its whole column anyway)
+    const int n = n_base + lane;
+    const bool want_cs = __builtin_amdgcn_readfirstlane(ep.colsum_part != nullptr ? 1 : 0) != 0;
+    const char* col = lds_wave + ((lane & 7) << 1);
+    unsigned sc4 = 0;
+    float cs = 0.f;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      float f[32];
+      float a = 0.f;
+#pragma unroll
+      for (int i = 0; i < 32; ++i) {
+        const int r = 32 * b + i;  // r & 7 == i & 7: eight per-lane addresses, the rest are immediate offsets
+        const unsigned h = *reinterpret_cast<const unsigned short*>(col + r * 128 + (((lane >> 3) ^ (i & 7)) << 4));
+        f[i] = __uint_as_float(h << 16);
+        a = fmaxf(a, fabsf(f[i]));
+        cs += f[i];
+      }
+      const int e = mx_exp(a);
+      unsigned w[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) w[k] = mx_pack4(f[4 * k], f[4 * k + 1], f[4 * k + 2], f[4 * k + 3], e);
+      if (n < N) {
+        uint8_t* dst = ep.mx_qt + (int64_t)n * Mp + m_base + 32 * b;
+        *reinterpret_cast<uint4*>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
+        *reinterpret_cast<uint4*>(dst + 16) = make_uint4(w[4], w[5], w[6], w[7]);
+      }
+      sc4 |= (unsigned)(e + 127) << (8 * b);
+      asm volatile("" ::: "memory");  // (as above: one block at a time)
+    }
+    if (n < N) {
+      *reinterpret_cast<unsigned*>(ep.mx_st + (int64_t)n * (Mp / 32) + (m_base >> 5)) = sc4;  // m_base % 128 == 0
+      if (want_cs) ep.colsum_part[(int64_t)(m_base >> 7) * N + n] = cs;  // one partial row per 128-row wave tile
+    }
+  }
+}
+
+// one specialised body per activation the MXFP8-output GEMM takes (0, 2 GELU, 3 GELU backward)
+__device__ __forceinline__ void gemm256_store_mx(const dev::f32x4 (&acc)[8][4], const GemmEpilogue& ep, int M, int N,
+                                                 int mrow, int ncol, char* lds_wave) {
+  const EpiFlags fl = epi_flags(ep);
+  switch (fl.act) {
+    case 2: gemm256_mx_to_lds<2>(acc, ep, fl, M, N, mrow, ncol, ep.alpha, lds_wave); break;
+    case 3: gemm256_mx_to_lds<3>(acc, ep, fl, M, N, mrow, ncol, ep.alpha, lds_wave); break;
+    default: gemm256_mx_to_lds<0>(acc, ep, fl, M, N, mrow, ncol, ep.alpha, lds_wave); break;
+  }
+  gemm256_mx_from_lds(ep, M, N, mrow, ncol, lds_wave);
 }
 
 // QUAD: the phased kernel's tile order (acc[qm*4 + mt][qn*2 + nt], quadrants of 64 rows x 32 cols);

@@ -34,6 +34,8 @@
 // Epilogue: gemm256_store without the e4m3-output path (bias, GELU, residual, pre-activation copy; split-K fp32
 // partial planes), dequantisation scale 1 - the block scales are already applied inside the MFMA.  Edge
 // tiles: source rows are clamped (operands and scales), rows / columns past the edge are dropped on store.
+// A second instantiation (MXOUT) ends in gemm256_store_mx instead: the same values leave as MXFP8 in both
+// orientations (what mx_quantize would make of the bf16 C), with their column sums, for the next GEMMs.
 #include <algorithm>
 
 #include "device_common.h"
@@ -78,6 +80,8 @@ __device__ __forceinline__ void raw_barrier() {
   asm volatile("" ::: "memory");
 }
 
+// MXOUT: the epilogue writes MXFP8 (gemm256_store_mx) instead of bf16 / fp32 / split-K planes
+template <bool MXOUT>
 __global__ __launch_bounds__(512, 1) void gemm_mxfp8_256_kernel(const uint8_t* __restrict__ A,
                                                                const uint8_t* __restrict__ SA,
                                                                const uint8_t* __restrict__ B,
@@ -187,7 +191,10 @@ __global__ __launch_bounds__(512, 1) void gemm_mxfp8_256_kernel(const uint8_t* _
   //                  n = n0 + wn*64 + 16j + 4*(lane>>4)
   const int mrow = m0 + wm * 128 + (lane & 15);
   const int ncol = n0 + wn * 64 + 4 * (lane >> 4);
-  gemm256_store<false, false>(acc, ep, M, N, split, 0, mrow, ncol, 1.f, smem + wave * 16384);
+  if constexpr (MXOUT)
+    gemm256_store_mx(acc, ep, M, N, mrow, ncol, smem + wave * 16384);
+  else
+    gemm256_store<false, false>(acc, ep, M, N, split, 0, mrow, ncol, 1.f, smem + wave * 16384);
 }
 
 }  // namespace
@@ -195,7 +202,9 @@ __global__ __launch_bounds__(512, 1) void gemm_mxfp8_256_kernel(const uint8_t* _
 int gemm_mxfp8_256(const uint8_t* A, const uint8_t* sa, const uint8_t* B, const uint8_t* sb, int M, int N, int Kbytes,
                    const GemmEpilogue& ep, int splits, hipStream_t s) {
   const int tiles_m = (M + TM - 1) / TM, tiles_n = (N + TN - 1) / TN;
-  splits = std::max(1, splits);
+  const bool mxout = ep.mx_q != nullptr;
+  if (mxout && ep.mode != GemmEpilogue::kStore) return 0;
+  splits = mxout ? 1 : std::max(1, splits);
   int kps = (Kbytes + splits - 1) / splits;
   kps = (kps + TK - 1) / TK * TK;
   splits = (Kbytes + kps - 1) / kps;
@@ -203,8 +212,11 @@ int gemm_mxfp8_256(const uint8_t* A, const uint8_t* sa, const uint8_t* B, const 
   e2.store_mode = 1;  // bf16 output: 16-B stores after a lane exchange, as the per-tensor e4m3 kernel
   e2.store_rot = true;
   e2.store_cache = gemm_store_cache();
-  gemm_mxfp8_256_kernel<<<dim3(tiles_m * tiles_n, splits), 512, 0, s>>>(A, sa, B, sb, e2, M, N, Kbytes, tiles_m,
-                                                                       tiles_n, kps);
+  const dim3 grid(tiles_m * tiles_n, splits);
+  if (mxout)
+    gemm_mxfp8_256_kernel<true><<<grid, 512, 0, s>>>(A, sa, B, sb, e2, M, N, Kbytes, tiles_m, tiles_n, kps);
+  else
+    gemm_mxfp8_256_kernel<false><<<grid, 512, 0, s>>>(A, sa, B, sb, e2, M, N, Kbytes, tiles_m, tiles_n, kps);
   return splits;
 }
 

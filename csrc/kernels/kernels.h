@@ -412,6 +412,14 @@ struct GemmEpilogue {
   float* q8_scale;
   float* q8_tmax;
   float* colsum_part;
+  // MXFP8 outputs instead of C (gemm_mxfp8_256 only; all four or none, never with kSplitK): the final value
+  // (bf16-rounded, as above) quantised as mx_quantize would quantise the stored C, in both orientations:
+  // mx_q [M][Np] / mx_s [M][Np/32] and mx_qt [N][Mp] / mx_st [N][Mp/32], Np / Mp = mx_pad(N / M), N % 32 == 0,
+  // padding (zero bytes, scale 127) included.  colsum_part is then [mx_pad(M) / 128][N].
+  uint8_t* mx_q;
+  uint8_t* mx_s;
+  uint8_t* mx_qt;
+  uint8_t* mx_st;
 };
 struct ConvGeom {
   int N, H, W, C;   // input NHWC (C padded to a multiple of 8)
@@ -505,7 +513,8 @@ struct MxQuantTable {
 void mx_quantize_multi(const MxQuantTable& t, hipStream_t stream);
 // MXFP8 GEMM (gemm_mxfp8_256.hip): A [M][Kbytes], B [N][Kbytes] e4m3, sa [M][Kbytes/32], sb [N][Kbytes/32] E8M0,
 // Kbytes % 128 == 0, N % 4 == 0; ep as gemm_fp8's without scale_a/b, q8 and stats.  Returns the number of
-// k-splits launched (kSplitK: that many [M][N] planes of ep.partial were written).
+// k-splits launched (kSplitK: that many [M][N] planes of ep.partial were written).  With ep.mx_q set the
+// outputs are MXFP8 (see GemmEpilogue): one split, N % 32 == 0; 0 (nothing launched) if ep asks for split-K.
 int gemm_mxfp8_256(const uint8_t* A, const uint8_t* sa, const uint8_t* B, const uint8_t* sb, int M, int N, int Kbytes,
                    const GemmEpilogue& ep, int splits, hipStream_t s);
 // column sums of a bf16 [rows][cols] matrix as colsum_parts(rows) fp32 partial rows (sum them with splitk_sum;

@@ -23,6 +23,7 @@
 // two vertically adjacent blocks and writes their scales as one 16-bit store.
 #include "device_common.h"
 #include "kernels.h"
+#include "mx_device.h"
 
 namespace ringdp {
 namespace kern {
@@ -42,19 +43,6 @@ __device__ __forceinline__ void load16(const float* p, bf16x8& a, bf16x8& b) {  
   const float4 v0 = f[0], v1 = f[1], v2 = f[2], v3 = f[3];
   a = bf16x8{(bf16)v0.x, (bf16)v0.y, (bf16)v0.z, (bf16)v0.w, (bf16)v1.x, (bf16)v1.y, (bf16)v1.z, (bf16)v1.w};
   b = bf16x8{(bf16)v2.x, (bf16)v2.y, (bf16)v2.z, (bf16)v2.w, (bf16)v3.x, (bf16)v3.y, (bf16)v3.z, (bf16)v3.w};
-}
-
-// unbiased block exponent of a block with amax a >= 0 (see the header)
-__device__ __forceinline__ int mx_exp(float a) {
-  const unsigned u = __float_as_uint(a);
-  const int e = (int)(u >> 23) - 135 + ((u & 0x7fffffu) > 0x600000u ? 1 : 0);
-  return u == 0 ? 0 : max(-127, min(127, e));
-}
-
-__device__ __forceinline__ unsigned pack4(float a, float b, float c, float d, int e) {
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(ldexpf(a, -e), ldexpf(b, -e), 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(ldexpf(c, -e), ldexpf(d, -e), w, true);
-  return (unsigned)w;
 }
 
 // One 128 x 128 tile (br, bc); q / qt null: that orientation is not wanted (uniform over the launch or entry).
@@ -93,8 +81,8 @@ __device__ __forceinline__ void mx_tile(const X* __restrict__ x, int64_t R, int6
       }
       a = fmaxf(a, __shfl_xor(a, 1, 64));  // the other half of this 32-value row block
       const int e = mx_exp(a);
-      const uint4 w = make_uint4(pack4(f[0], f[1], f[2], f[3], e), pack4(f[4], f[5], f[6], f[7], e),
-                                 pack4(f[8], f[9], f[10], f[11], e), pack4(f[12], f[13], f[14], f[15], e));
+      const uint4 w = make_uint4(mx_pack4(f[0], f[1], f[2], f[3], e), mx_pack4(f[4], f[5], f[6], f[7], e),
+                                 mx_pack4(f[8], f[9], f[10], f[11], e), mx_pack4(f[12], f[13], f[14], f[15], e));
       // the row's four scale bytes (lanes 0 / 2 / 4 / 6 of its 8) into one dword on the first lane
       const unsigned sb = (unsigned)(e + 127);
       const int l0 = lane & ~7;
@@ -125,7 +113,7 @@ __device__ __forceinline__ void mx_tile(const X* __restrict__ x, int64_t R, int6
     const int e = mx_exp(a);
     unsigned w[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) w[k] = pack4(f[4 * k], f[4 * k + 1], f[4 * k + 2], f[4 * k + 3], e);
+    for (int k = 0; k < 8; ++k) w[k] = mx_pack4(f[4 * k], f[4 * k + 1], f[4 * k + 2], f[4 * k + 3], e);
     uint8_t* dst = qt + gc2 * Rp + (int64_t)br * kT + r0;
     *reinterpret_cast<uint4*>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
     *reinterpret_cast<uint4*>(dst + 16) = make_uint4(w[4], w[5], w[6], w[7]);

@@ -138,6 +138,60 @@ at::Tensor gemm_mxfp8(const at::Tensor& a, const at::Tensor& sa, const at::Tenso
   return c;
 }
 
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> gemm_mxfp8_quant_out(
+    const at::Tensor& a, const at::Tensor& sa, const at::Tensor& b, const at::Tensor& sb, int64_t M, int64_t N,
+    int64_t K, const c10::optional<at::Tensor>& bias, int64_t act, const c10::optional<at::Tensor>& preact,
+    const c10::optional<at::Tensor>& colsum) {
+  mx_gemm_dims(M, N, K, "gemm_mxfp8_quant_out");
+  RINGDP_CHECK(N % 32 == 0, "gemm_mxfp8_quant_out: N must hold whole blocks of 32, got ", N);
+  mx_operand(a, sa, M, K, "gemm_mxfp8_quant_out A");
+  mx_operand(b, sb, N, K, "gemm_mxfp8_quant_out B");
+  RINGDP_CHECK(act == 0 || act == 2 || act == 3,
+               "gemm_mxfp8_quant_out: act must be 0, 2 (GELU) or 3 (GELU backward)");
+  c10::DeviceGuard guard(a.device());
+  kern::GemmEpilogue e{};
+  e.mode = kern::GemmEpilogue::kStore;
+  e.ldc = N;  // of preact: the values themselves never reach memory
+  e.out_bf16 = true;
+  e.alpha = 1.f;
+  e.act = static_cast<int>(act);
+  if (bias.has_value() && bias->defined()) {
+    f32_gpu(*bias, "gemm_mxfp8_quant_out bias");
+    RINGDP_CHECK(bias->numel() == N && reinterpret_cast<uintptr_t>(bias->data_ptr()) % 16 == 0,
+                 "gemm_mxfp8_quant_out bias: expected [N] floats, 16-B aligned");
+    e.bias = bias->data_ptr<float>();
+  }
+  const bool has_pre = preact.has_value() && preact->defined();
+  RINGDP_CHECK(has_pre == (act != 0), "gemm_mxfp8_quant_out: act 2 writes and act 3 reads preact; act 0 takes none");
+  if (has_pre) {
+    bf16_gpu(*preact, "gemm_mxfp8_quant_out preact");
+    RINGDP_CHECK(preact->numel() == M * N && preact->is_contiguous() &&
+                     reinterpret_cast<uintptr_t>(preact->data_ptr()) % 8 == 0,
+                 "gemm_mxfp8_quant_out preact: expected contiguous [M][N], 8-B aligned");
+    e.preact = preact->data_ptr();
+  }
+  const int64_t Mp = kern::mx_pad(M), Np = kern::mx_pad(N);
+  // (torch.empty: the kernel writes every byte, padding included)
+  at::Tensor q = at::empty({M, Np}, a.options()), s = at::empty({M, Np / 32}, a.options());
+  at::Tensor qt = at::empty({N, Mp}, a.options()), st = at::empty({N, Mp / 32}, a.options());
+  e.mx_q = u8(q);
+  e.mx_s = u8(s);
+  e.mx_qt = u8(qt);
+  e.mx_st = u8(st);
+  at::Tensor part;
+  if (colsum.has_value() && colsum->defined()) {
+    f32_gpu(*colsum, "gemm_mxfp8_quant_out colsum");
+    RINGDP_CHECK(colsum->numel() == N && colsum->is_contiguous(), "gemm_mxfp8_quant_out colsum: expected [N] floats");
+    part = at::empty({Mp / 128, N}, colsum->options());  // one partial row per 128-row wave tile
+    e.colsum_part = part.data_ptr<float>();
+  }
+  const int used = kern::gemm_mxfp8_256(u8(a), u8(sa), u8(b), u8(sb), (int)M, (int)N, (int)K, e, 1, stream_of(a));
+  RINGDP_CHECK(used == 1, "gemm_mxfp8_quant_out: the MXFP8-output kernel was not launched");
+  if (part.defined())
+    kern::rowsum_f32(part.data_ptr<float>(), (int)part.size(0), N, colsum->data_ptr<float>(), stream_of(a));
+  return {q, s, qt, st};
+}
+
 void gemm_mxfp8_splitk_f32(const at::Tensor& a, const at::Tensor& sa, const at::Tensor& b, const at::Tensor& sb,
                            int64_t M, int64_t N, int64_t K, int64_t splits, at::Tensor out) {
   mx_gemm_dims(M, N, K, "gemm_mxfp8_splitk_f32");

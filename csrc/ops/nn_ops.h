@@ -155,6 +155,14 @@ std::vector<at::Tensor> mx_quantize_weights(const std::vector<at::Tensor>& ws); 
 at::Tensor gemm_mxfp8(const at::Tensor& a, const at::Tensor& sa, const at::Tensor& b, const at::Tensor& sb, int64_t M,
                       int64_t N, int64_t K, bool out_bf16, const c10::optional<at::Tensor>& bias, int64_t act,
                       const c10::optional<at::Tensor>& residual, const c10::optional<at::Tensor>& preact);
+// gemm_mxfp8 whose output leaves as MXFP8 in both orientations, (q [M][Np], s, qt [N][Mp], st) - the bytes
+// mx_quantize would make of the bf16 output, which is never stored.  N % 32 == 0; act 0, 2 (GELU; writes the bf16
+// pre-activation into preact) or 3 (GELU backward; reads preact); colsum (nullable, fp32 [N]) <- column sums of
+// the bf16-rounded values
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> gemm_mxfp8_quant_out(
+    const at::Tensor& a, const at::Tensor& sa, const at::Tensor& b, const at::Tensor& sb, int64_t M, int64_t N,
+    int64_t K, const c10::optional<at::Tensor>& bias, int64_t act, const c10::optional<at::Tensor>& preact,
+    const c10::optional<at::Tensor>& colsum);
 void gemm_mxfp8_splitk_f32(const at::Tensor& a, const at::Tensor& sa, const at::Tensor& b, const at::Tensor& sb,
                            int64_t M, int64_t N, int64_t K, int64_t splits, at::Tensor out);
 

@@ -31,8 +31,9 @@ import torch
 import torch.nn as nn
 
 from ..ops.dropout import DropoutF, drop_path_rows, drop_path_schedule, dropout_add, quantize_p
-from ..ops.transformer import (AttentionF, ClassRowsF, LayerNormF, LayerNormFork, MLPF, MLPF8, PatchTokensF,
-                                cast_weights, clear_weights, fp8_enabled, fp8_mlp_fusable, layernorm_fork, linear)
+from ..ops.transformer import (AttentionF, ClassRowsF, LayerNormF, LayerNormFork, MLPF, MLPF8, MLPMX, PatchTokensF,
+                                cast_weights, clear_weights, fp8_enabled, fp8_mlp_fusable, layernorm_fork, linear,
+                                mx_mlp_fusable)
 from ..random import Draw
 
 
@@ -110,9 +111,11 @@ class EncoderBlock(nn.Module):
             o = AttentionF.apply(qkv, B, T, self.num_heads)
             x = linear(o, att.out_proj, residual=x)
             h, x = layernorm_fork(x, self.ln_2, fc1.weight)
-            # per-tensor recipe: e4m3 from the GEMM epilogues; the MXFP8 recipe runs the plain linears below
+            # e4m3 (per-tensor recipe) or MXFP8 from the GEMM epilogues; otherwise the plain linears below
             if fp8_mlp_fusable(h.shape[0], h.shape[1], fc1.weight.shape[0]):
                 return MLPF8.apply(h, fc1.weight, fc1.bias, fc2.weight, fc2.bias, x)
+            if mx_mlp_fusable(h.shape[0], h.shape[1], fc1.weight.shape[0]):
+                return MLPMX.apply(h, fc1.weight, fc1.bias, fc2.weight, fc2.bias, x)
             h = linear(h, fc1, act=2)
             return linear(h, fc2, residual=x)
         # bf16: the residual streams' gradients join in the LayerNorm backward kernels (LayerNormFork)

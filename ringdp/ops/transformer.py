@@ -509,6 +509,72 @@ def _linear_mx_bwd(ctx, dy):
     return dx, dw, db, dres, None, None
 
 
+# MXFP8 recipe: the MLP's [tokens, hidden] tensors leave their GEMM epilogues as MXFP8 (RINGDP_MX_MLP_FUSED=0: the
+# unfused MXFP8 linears, for A/B runs)
+_MX_MLP_FUSED = os.environ.get("RINGDP_MX_MLP_FUSED", "1") != "0"
+
+
+def mx_mlp_fusable(M: int, D: int, Hd: int) -> bool:
+    """MLPMX needs whole 128-byte k-steps for fc1 (K = D, as MLPF8) and whole 32-blocks along the hidden axis;
+    any number of rows."""
+    return _FP8["mx"] and _MX_MLP_FUSED and D % 128 == 0 and Hd % 32 == 0
+
+
+class MLPMX(torch.autograd.Function):
+    """The transformer MLP ``y = fc2(GELU(fc1(h))) + residual`` in MXFP8 with the [tokens, hidden] tensors
+    quantised by the GEMM epilogues that produce them (``gemm_mxfp8_quant_out``):
+      forward   fc1's epilogue applies bias + GELU, stores the bf16 pre-activation and writes GELU(.) as MXFP8
+                blocked along the hidden axis (fc2's A) and along the tokens (fc2's weight gradient);
+      backward  fc2's data-gradient epilogue applies the GELU backward and writes dz1 as MXFP8 in both
+                orientations plus its column sums (fc1's bias gradient).
+    Neither bf16 tensor reaches memory and neither is read back by mx_quantize.  The scales come from the data in
+    the epilogue itself: no sites, no histories, no first-call path (compare MLPF8)."""
+
+    @staticmethod
+    def forward(ctx, h, w1, b1, w2, b2, residual):
+        M, D = h.shape
+        Hd = w1.shape[0]
+        hq, hs, hqt, hst = C.mx_quantize(h.contiguous(), True, True)
+        w1q, w1s, w1qt, w1st = _mx_weight(w1)
+        w2q, w2s, w2qt, w2st = _mx_weight(w2)
+        pre = torch.empty(M, Hd, device=h.device, dtype=torch.bfloat16)
+        aq, as_, aqt, ast = C.gemm_mxfp8_quant_out(hq, hs, w1q, w1s, M, Hd, hq.shape[1], b1, 2, pre)
+        y = C.gemm_mxfp8(aq, as_, w2q, w2s, M, D, aq.shape[1], True, b2, 0, residual)
+        # (the weights' column-wise copies are saved: _MX_WEIGHTS is cleared after the forward)
+        ctx.save_for_backward(hqt, hst, w1qt, w1st, pre, aqt, ast, w2qt, w2st)
+        ctx.params = (w1, b1, w2, b2)
+        ctx.dims = (M, D, Hd)
+        ctx.has_res = residual is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        hqt, hst, w1qt, w1st, pre, aqt, ast, w2qt, w2st = ctx.saved_tensors
+        w1, b1, w2, b2 = ctx.params
+        M, D, Hd = ctx.dims
+        n = ctx.needs_input_grad
+        dyb = dy.contiguous() if dy.dtype == torch.bfloat16 else _bf16(dy)
+        dyq, dys, dyqt, dyst = C.mx_quantize(dyb, True, True)  # blocks along D for dz1, along the tokens for dW2
+        db2 = None
+        if n[4]:
+            db2 = grad_buffer(b2)
+            C.colsum_f32(dyb, db2)
+        dw2 = None
+        if n[3]:  # dW2[d][j] = sum_m dy[m][d] a[m][j]
+            dw2 = grad_buffer(w2)
+            C.gemm_mxfp8_splitk_f32(dyqt, dyst, aqt, ast, D, Hd, dyqt.shape[1], _splits(M, D, Hd), dw2)
+        # dz1 = (dy W2) * GELU'(pre) and its column sums, straight from the GEMM epilogue as MXFP8
+        db1 = grad_buffer(b1) if n[2] else None
+        dzq, dzs, dzqt, dzst = C.gemm_mxfp8_quant_out(dyq, dys, w2qt, w2st, M, Hd, dyq.shape[1], None, 3, pre, db1)
+        dw1 = None
+        if n[1]:  # dW1[j][d] = sum_m dz1[m][j] h[m][d]
+            dw1 = grad_buffer(w1)
+            C.gemm_mxfp8_splitk_f32(dzqt, dzst, hqt, hst, Hd, D, dzqt.shape[1], _splits(M, Hd, D), dw1)
+        dh = C.gemm_mxfp8(dzq, dzs, w1qt, w1st, M, D, dzq.shape[1], True) if n[0] else None
+        dres = dyb if ctx.has_res and n[5] else None
+        return dh, dw1, db1, dw2, db2, dres
+
+
 class MLPF(torch.autograd.Function):
     """The transformer MLP ``y = fc2(GELU(fc1(h))) + residual`` as one Function (bf16 path), so that
     the backward runs the GELU derivative inside fc2's data-gradient GEMM epilogue (ringdp's act-3

@@ -4,7 +4,9 @@ GEMM: ``gemm_mxfp8`` vs ``gemm_fp8`` (bf16 output, no epilogue extras) on the Vi
 benchmark batch (tokens = 128 x 197) and at 8192^3, as TF/s from 2 M N K over device-event time.
 Quantiser: ``mx_quantize`` (both orientations) vs ``fp8_quantize_both_delayed`` on the [tokens, 768] and
 [tokens, 3072] activations, as GB/s of the bytes each must move (one bf16 read, two e4m3 writes, plus MX scales).
-The two variants of a row are timed alternately, ``--rounds`` windows each; the median and the spread are printed.
+MLP epilogue: ``gemm_mxfp8_quant_out`` on the two [tokens, 3072] x 768 MLP GEMMs (act 2 and act 3) vs the passes it
+replaces and vs the GEMM alone.
+The variants of a row are timed alternately, ``--rounds`` windows each; the median and the spread are printed.
 One JSON line per row.
 """
 from __future__ import annotations
@@ -83,11 +85,55 @@ def bench_quant(R: int, Cc: int, iters: int, rounds: int) -> dict:
             "mx_gbs": round((byt + 2 * R * Cc / 32) / m / 1e6, 1), "tensor_gbs": round(byt / p / 1e6, 1)}
 
 
+def bench_mlp(M: int, N: int, K: int, act: int, iters: int, rounds: int) -> dict:
+    """The MXFP8-writing epilogue on an MLP GEMM (act 2: fc1 forward with bias; act 3: fc2's data gradient with the
+    column sums) against the passes it replaces - the GEMM to bf16, ``mx_quantize`` of its output and, for act 3,
+    ``gelu_bwd`` and ``colsum_f32`` - and against that GEMM alone."""
+    a = torch.randn(M, K, device="cuda").bfloat16()
+    b = (torch.randn(N, K, device="cuda") / K ** 0.5).bfloat16()
+    aq, sa, _, _ = C.mx_quantize(a, True, False)
+    bq, sb, _, _ = C.mx_quantize(b, True, False)
+    Kp = aq.shape[1]
+    pre = torch.randn(M, N, device="cuda").bfloat16()
+    bias = torch.randn(N, device="cuda") if act == 2 else None
+    cs = torch.empty(N, device="cuda") if act == 3 else None
+
+    def fused():
+        C.gemm_mxfp8_quant_out(aq, sa, bq, sb, M, N, Kp, bias, act, pre, cs)
+
+    def gemm_only():
+        return C.gemm_mxfp8(aq, sa, bq, sb, M, N, Kp, True, bias, 2 if act == 2 else 0, None, pre if act == 2 else None)
+
+    def passes():
+        y = gemm_only()
+        if act == 3:
+            y = C.gelu_bwd(y, pre)
+            C.colsum_f32(y, cs)
+        C.mx_quantize(y, True, True)
+
+    fns = (fused, passes, gemm_only)
+    for f in fns:
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    ts = [[], [], []]
+    for _ in range(rounds):  # alternating windows
+        for t, f in zip(ts, fns):
+            t.append(_time(f, iters))
+    out = {"kind": "mlp_epilogue", "M": M, "N": N, "K": K, "act": act}
+    for name, t in zip(("fused", "passes", "gemm_only"), ts):
+        m, lo, hi = _stats(t)
+        out[name + "_ms"] = round(m, 4)
+        out[name + "_ms_range"] = [round(lo, 4), round(hi, 4)]
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--batch", type=int, default=128, help="images per step (197 tokens each)")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--only-mlp", action="store_true", help="only the MLP-epilogue rows")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mxfp8_bench: needs a GPU")
@@ -97,10 +143,12 @@ def main() -> None:
     Tk = T // 128 * 128
     shapes = [(T, 2304, 768, 1), (T, 768, 768, 1), (T, 3072, 768, 1), (T, 768, 3072, 1), (T, 768, 2304, 1),
               (3072, 768, Tk, 4), (768, 3072, Tk, 4), (8192, 8192, 8192, 1)]
-    for M, N, K, splits in shapes:
+    for M, N, K, splits in ([] if args.only_mlp else shapes):
         print(json.dumps(bench_gemm(M, N, K, splits, args.iters, args.rounds)), flush=True)
-    for R, Cc in ((T, 768), (T, 3072)):
+    for R, Cc in (() if args.only_mlp else ((T, 768), (T, 3072))):
         print(json.dumps(bench_quant(R, Cc, args.iters, args.rounds)), flush=True)
+    for act in (2, 3):  # fc1 forward, fc2 data gradient: [tokens, 3072] out of K = 768
+        print(json.dumps(bench_mlp(T, 3072, 768, act, args.iters, args.rounds)), flush=True)
 
 
 if __name__ == "__main__":
