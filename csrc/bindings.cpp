@@ -682,6 +682,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "MXFP8 (e4m3 + E8M0 per block of 32) of a bf16 / fp32 matrix: (q, s, qt, st), the orientation not asked for None");
   m.def("mx_quantize_weights", &ops::mx_quantize_weights,
         "MXFP8 copies, both orientations, of many fp32 weights in one launch: flat (q, s, qt, st) per weight");
+  m.def("layernorm_fwd_mx", &ops::layernorm_fwd_mx, py::arg("x"), py::arg("w"), py::arg("b"), py::arg("eps"),
+        py::arg("colwise"),
+        "layernorm forward with MXFP8 outputs: (stats, q, s, qt, st), the bytes of mx_quantize(layernorm_fwd(x)); "
+        "qt, st None without colwise");
   m.def("gemm_mxfp8", &ops::gemm_mxfp8, py::arg("a"), py::arg("sa"), py::arg("b"), py::arg("sb"), py::arg("M"),
         py::arg("N"), py::arg("K"), py::arg("out_bf16") = true, py::arg("bias") = py::none(), py::arg("act") = 0,
         py::arg("residual") = py::none(), py::arg("preact") = py::none());

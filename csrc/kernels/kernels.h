@@ -652,6 +652,12 @@ int layernorm_bwd_scratch_floats(int64_t rows, int D);
 int64_t layernorm_q8_blocks(int64_t rows);
 void layernorm_fwd_q8(const void* x, const float* w, const float* b, int64_t rows, int D, float eps, float* stats,
                       const float* amax, void* q, void* qt, float* scale, float* tmax, hipStream_t s);
+// LayerNorm forward with MXFP8 outputs (layernorm_mx.hip): the bytes mx_quantize writes for layernorm_fwd's bf16
+// output, padding included - q [rows][Cp], s [rows][Cp/32] and, unless qt is null, qt [D][Rp], st [D][Rp/32]
+// (Cp / Rp = mx_pad(D / rows)); stats as layernorm_fwd.  D % 32 == 0, 32 <= D <= 2048; x 16-B aligned;
+// dynamic LDS 64 * D bytes when qt is set
+void layernorm_fwd_mx(const void* x, const float* w, const float* b, int64_t rows, int D, float eps, float* stats,
+                      uint8_t* q, uint8_t* s, uint8_t* qt, uint8_t* st, hipStream_t stream);
 // cs_part (nullable): [layernorm_bwd_blocks(rows)][D] per-block column sums of dx (the bias gradient of the
 // linear whose output gradient dx is)
 int layernorm_bwd_blocks(int64_t rows);

@@ -68,6 +68,41 @@ mx_quantize(const at::Tensor& x, bool rowwise, bool colwise) {
   return {q, s, qt, st};
 }
 
+std::tuple<at::Tensor, at::Tensor, at::Tensor, c10::optional<at::Tensor>, c10::optional<at::Tensor>> layernorm_fwd_mx(
+    const at::Tensor& x, const at::Tensor& w, const at::Tensor& b, double eps, bool colwise) {
+  gpu(x, "layernorm_fwd_mx input");
+  dtype(x, at::kBFloat16, "layernorm_fwd_mx input");
+  RINGDP_CHECK(x.dim() == 2 && x.is_contiguous() && x.size(0) >= 1, "layernorm_fwd_mx input: expected contiguous [rows >= 1, D], got ",
+               x.sizes());
+  const int64_t rows = x.size(0), D = x.size(1);
+  RINGDP_CHECK(D % 32 == 0 && D >= 32 && D <= 2048, "layernorm_fwd_mx: expected D % 32 == 0 and 32 <= D <= 2048, got ", D);
+  RINGDP_CHECK(rows < (int64_t(1) << 31) - 128, "layernorm_fwd_mx: too many rows");
+  f32_gpu(w, "layernorm_fwd_mx weight");
+  f32_gpu(b, "layernorm_fwd_mx bias");
+  RINGDP_CHECK(w.numel() == D && b.numel() == D && w.is_contiguous() && b.is_contiguous() &&
+                   w.get_device() == x.get_device() && b.get_device() == x.get_device(),
+               "layernorm_fwd_mx: weight and bias must be contiguous [D] on the input's device");
+  RINGDP_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, "layernorm_fwd_mx input: expected a 16-B aligned tensor");
+  c10::DeviceGuard guard(x.device());
+  const int64_t Rp = kern::mx_pad(rows), Cp = kern::mx_pad(D);
+  const auto o = x.options().dtype(at::kByte);
+  at::Tensor stats = at::empty({rows, 2}, w.options());
+  // (at::empty: the kernel writes every byte, padding included)
+  at::Tensor q = at::empty({rows, Cp}, o), s = at::empty({rows, Cp / 32}, o);
+  c10::optional<at::Tensor> qt, st;
+  if (colwise) {
+    qt = at::empty({D, Rp}, o);
+    st = at::empty({D, Rp / 32}, o);
+  }
+  kern::layernorm_fwd_mx(x.data_ptr(), w.data_ptr<float>(), b.data_ptr<float>(), rows, (int)D, (float)eps,
+                         stats.data_ptr<float>(), u8(q), u8(s), colwise ? u8(*qt) : nullptr, colwise ? u8(*st) : nullptr,
+                         stream_of(x));
+  // with colwise the kernel takes 64 * D bytes of dynamic LDS (128 KiB at D = 2048): a launch the runtime refuses
+  // must not leave the outputs unwritten without a word
+  RINGDP_HIP_CHECK(hipGetLastError());
+  return {stats, q, s, qt, st};
+}
+
 std::vector<at::Tensor> mx_quantize_weights(const std::vector<at::Tensor>& ws) {
   RINGDP_CHECK(!ws.empty(), "mx_quantize_weights: no weights");
   c10::DeviceGuard guard(ws[0].device());

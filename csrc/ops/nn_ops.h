@@ -152,6 +152,10 @@ void gemm_fp8_splitk_f32(const at::Tensor& a, const at::Tensor& b, const at::Ten
 std::tuple<c10::optional<at::Tensor>, c10::optional<at::Tensor>, c10::optional<at::Tensor>, c10::optional<at::Tensor>>
 mx_quantize(const at::Tensor& x, bool rowwise, bool colwise);
 std::vector<at::Tensor> mx_quantize_weights(const std::vector<at::Tensor>& ws);  // fp32 weights -> flat (q, s, qt, st)...
+// LayerNorm forward whose output leaves as MXFP8: (stats, q, s, qt | None, st | None), the bytes mx_quantize would
+// make of layernorm_fwd's bf16 output, which is never stored.  x [rows, D] bf16, D % 32 == 0, 32 <= D <= 2048
+std::tuple<at::Tensor, at::Tensor, at::Tensor, c10::optional<at::Tensor>, c10::optional<at::Tensor>> layernorm_fwd_mx(
+    const at::Tensor& x, const at::Tensor& w, const at::Tensor& b, double eps, bool colwise);
 at::Tensor gemm_mxfp8(const at::Tensor& a, const at::Tensor& sa, const at::Tensor& b, const at::Tensor& sb, int64_t M,
                       int64_t N, int64_t K, bool out_bf16, const c10::optional<at::Tensor>& bias, int64_t act,
                       const c10::optional<at::Tensor>& residual, const c10::optional<at::Tensor>& preact);

@@ -42,6 +42,7 @@ UNIT_FLAGS = {
     "resize_crop.hip": _NO_PK_F32,
     "mxfp8.hip": _NO_PK_F32,
     "gemm_mxfp8_256.hip": _NO_PK_F32,
+    "layernorm_mx.hip": _NO_PK_F32,
 }
 
 

@@ -189,6 +189,9 @@ class LinearF(torch.autograd.Function):
         if getattr(x, "_ringdp_q8", None) is not None:
             raise RuntimeError("LinearF: x is an e4m3-only LayerNorm output (LayerNormFork8) but this linear "
                                "is not on the fp8 path")
+        if getattr(x, "_ringdp_mx", None) is not None:
+            raise RuntimeError("LinearF: x is an MXFP8-only LayerNorm output (LayerNormForkMX) but this linear "
+                               "is not on the MXFP8 path")
         Np = (N + 7) // 8 * 8  # the weight-gradient GEMM walks rows of W in 16-B vectors
         wb = _bf16(w)
         bb = b
@@ -474,7 +477,7 @@ def _linear_mx_fwd(ctx, x, w, b, residual, act, out_f32):
     M, K = x.shape
     N = w.shape[0]
     want_dw = ctx.needs_input_grad[1]
-    xq, xs, xqt, xst = C.mx_quantize(x.contiguous(), True, want_dw)  # blocks along K; along M for dW
+    xq, xs, xqt, xst = _mx_of(x, want_dw)                             # blocks along K; along M for dW
     wq, ws, wqt, wst = _mx_weight(w)                                  # blocks along K; along N for dx
     pre = torch.empty(M, N, device=x.device, dtype=torch.bfloat16) if act == 2 else None
     y = C.gemm_mxfp8(xq, xs, wq, ws, M, N, xq.shape[1], not out_f32, b, act, residual, pre)
@@ -501,6 +504,7 @@ def _linear_mx_bwd(ctx, dy):
         dx = C.gemm_mxfp8(dzq, dzs, wqt, wst, M, K, dzq.shape[1], True)
     if want_dw:  # dW[n][k] = sum_m dz[m][n] x[m][k]: both column-wise, blocked along m
         dw = grad_buffer(w)
+        xqt = _mx_need_t(xqt, "LinearF")
         C.gemm_mxfp8_splitk_f32(dzqt, dzst, xqt, xst, N, K, dzqt.shape[1], _splits(M, N, K), dw)
     if b is not None and ctx.needs_input_grad[2]:
         db = grad_buffer(b)
@@ -534,7 +538,7 @@ class MLPMX(torch.autograd.Function):
     def forward(ctx, h, w1, b1, w2, b2, residual):
         M, D = h.shape
         Hd = w1.shape[0]
-        hq, hs, hqt, hst = C.mx_quantize(h.contiguous(), True, True)
+        hq, hs, hqt, hst = _mx_of(h, True)  # (hqt None: a LayerNorm's that was told no dW1 is wanted)
         w1q, w1s, w1qt, w1st = _mx_weight(w1)
         w2q, w2s, w2qt, w2st = _mx_weight(w2)
         pre = torch.empty(M, Hd, device=h.device, dtype=torch.bfloat16)
@@ -569,6 +573,7 @@ class MLPMX(torch.autograd.Function):
         dw1 = None
         if n[1]:  # dW1[j][d] = sum_m dz1[m][j] h[m][d]
             dw1 = grad_buffer(w1)
+            hqt = _mx_need_t(hqt, "MLPMX")
             C.gemm_mxfp8_splitk_f32(dzqt, dzst, hqt, hst, Hd, D, dzqt.shape[1], _splits(M, Hd, D), dw1)
         dh = C.gemm_mxfp8(dzq, dzs, w1qt, w1st, M, D, dzq.shape[1], True) if n[0] else None
         dres = dyb if ctx.has_res and n[5] else None
@@ -705,11 +710,65 @@ def _fork8_ok(x, consumer_w) -> bool:
         and consumer_w.shape[-1] == d
 
 
+# MXFP8 recipe: the LayerNorm in front of an MXFP8 linear writes MXFP8 itself (RINGDP_MX_LN_FUSED=0: bf16 rows
+# that the linear quantises in a pass of its own, for A/B runs)
+_MX_LN_FUSED = os.environ.get("RINGDP_MX_LN_FUSED", "1") != "0"
+
+
+class LayerNormForkMX(torch.autograd.Function):
+    """LayerNormFork for an MXFP8 consumer: the forward writes the normalised rows as MXFP8 (blocks along the row
+    and, when the consumer's weight gradient is wanted, along the column, stored transposed) instead of bf16 -
+    byte for byte what ``mx_quantize`` makes of LayerNormFork's rows - so the consumer needs no quantisation pass.
+    The returned ``y`` is an unwritten placeholder carrying ``(q, s, qt, st)`` (``_ringdp_mx``), read only by
+    LinearF / MLPMX; the backward is LayerNormFork's.  No sites, no first-call path (compare LayerNormFork8)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, eps: float, colwise: bool):
+        stats, q, s, qt, st = C.layernorm_fwd_mx(x, w, b, eps, colwise)
+        ctx.save_for_backward(x, stats)
+        ctx.params = (w, b)
+        y = torch.empty_like(x)
+        y._ringdp_mx = (q, s, qt, st)
+        return y, x
+
+    @staticmethod
+    def backward(ctx, dy, dres):
+        return (*LayerNormFork.backward(ctx, dy, dres), None)
+
+
+def _forkmx_ok(x, consumer_w) -> bool:
+    """LayerNormForkMX's placeholder ``y`` is only valid if the consumer takes the MXFP8 path (LinearF's
+    ``_mx_ok``; MLPMX asks for more of the same shapes), within the kernel's D % 32 == 0, D <= 2048."""
+    d = x.shape[-1]
+    return x.dim() == 2 and x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and d % 32 == 0 \
+        and d <= 2048 and consumer_w.shape[-1] == d and _mx_ok(d, consumer_w.shape[0])
+
+
 def layernorm_fork(x, ln, consumer_w):
-    """``y, x_id`` of LayerNormFork, or of LayerNormFork8 when the consumer is an fp8 linear."""
+    """``y, x_id`` of LayerNormFork, or of LayerNormFork8 / LayerNormForkMX when the consumer is an fp8 linear of
+    the per-tensor / MXFP8 recipe."""
     if _FP8["on"] and _FP8_LN_Q8 and _FP8_DELAYED and _fork8_ok(x, consumer_w):
         return LayerNormFork8.apply(x, ln.weight, ln.bias, ln.eps, consumer_w)
+    if _FP8["mx"] and _MX_LN_FUSED and _forkmx_ok(x, consumer_w):
+        # the column-wise bytes feed the consumer's weight gradient only
+        colwise = torch.is_grad_enabled() and consumer_w.requires_grad
+        return LayerNormForkMX.apply(x, ln.weight, ln.bias, ln.eps, colwise)
     return LayerNormFork.apply(x, ln.weight, ln.bias, ln.eps)
+
+
+def _mx_of(x, colwise: bool):
+    """(q, s, qt, st) of an MXFP8 GEMM input: from the producing LayerNorm (LayerNormForkMX; its qt / st are None
+    when it was told that no weight gradient is wanted, see _mx_need_t) or quantised here."""
+    e = getattr(x, "_ringdp_mx", None)
+    return e if e is not None else C.mx_quantize(x.contiguous(), True, colwise)
+
+
+def _mx_need_t(xqt, who: str):
+    """The weight-gradient GEMM's column-wise input; a LayerNormForkMX without colwise wrote none."""
+    if xqt is None:
+        raise RuntimeError(f"{who}: the weight gradient is wanted but the LayerNorm that produced the input wrote no "
+                           "column-wise MXFP8 (LayerNormForkMX without colwise)")
+    return xqt
 
 
 def _q8_of(x, w, slot=0):

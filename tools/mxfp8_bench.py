@@ -6,6 +6,7 @@ Quantiser: ``mx_quantize`` (both orientations) vs ``fp8_quantize_both_delayed`` 
 [tokens, 3072] activations, as GB/s of the bytes each must move (one bf16 read, two e4m3 writes, plus MX scales).
 MLP epilogue: ``gemm_mxfp8_quant_out`` on the two [tokens, 3072] x 768 MLP GEMMs (act 2 and act 3) vs the passes it
 replaces and vs the GEMM alone.
+LayerNorm: ``layernorm_fwd_mx`` vs ``layernorm_fwd`` + ``mx_quantize`` at [128 x 197, 768] and [32 x 577, 768].
 The variants of a row are timed alternately, ``--rounds`` windows each; the median and the spread are printed.
 One JSON line per row.
 """
@@ -128,12 +129,31 @@ def bench_mlp(M: int, N: int, K: int, act: int, iters: int, rounds: int) -> dict
     return out
 
 
+def bench_ln(R: int, D: int, iters: int, rounds: int) -> dict:
+    """``layernorm_fwd_mx`` (both orientations) against the two calls it replaces, ``layernorm_fwd`` and
+    ``mx_quantize`` of its rows.  GB/s from the bytes each must move: the fused call reads x (bf16) and writes two
+    e4m3 copies and their scales; the two calls also write the bf16 rows and read them back."""
+    x = torch.randn(R, D, device="cuda").bfloat16()
+    w, b = torch.rand(D, device="cuda") + 0.5, torch.randn(D, device="cuda")
+
+    def passes():
+        C.mx_quantize(C.layernorm_fwd(x, w, b, 1e-6)[0], True, True)
+
+    t_f, t_p = _pair(lambda: C.layernorm_fwd_mx(x, w, b, 1e-6, True), passes, iters, rounds)
+    byt = R * D * (2 + 2) + 2 * R * D / 32
+    (m, lo, hi), (p, plo, phi) = _stats(t_f), _stats(t_p)
+    return {"kind": "layernorm", "R": R, "D": D, "fused_ms": round(m, 4), "fused_ms_range": [round(lo, 4), round(hi, 4)],
+            "passes_ms": round(p, 4), "passes_ms_range": [round(plo, 4), round(phi, 4)],
+            "fused_gbs": round(byt / m / 1e6, 1), "passes_gbs": round((byt + R * D * 4) / p / 1e6, 1)}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--batch", type=int, default=128, help="images per step (197 tokens each)")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--only-mlp", action="store_true", help="only the MLP-epilogue rows")
+    ap.add_argument("--only-ln", action="store_true", help="only the LayerNorm rows")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mxfp8_bench: needs a GPU")
@@ -143,12 +163,15 @@ def main() -> None:
     Tk = T // 128 * 128
     shapes = [(T, 2304, 768, 1), (T, 768, 768, 1), (T, 3072, 768, 1), (T, 768, 3072, 1), (T, 768, 2304, 1),
               (3072, 768, Tk, 4), (768, 3072, Tk, 4), (8192, 8192, 8192, 1)]
-    for M, N, K, splits in ([] if args.only_mlp else shapes):
+    only = args.only_mlp or args.only_ln
+    for M, N, K, splits in ([] if only else shapes):
         print(json.dumps(bench_gemm(M, N, K, splits, args.iters, args.rounds)), flush=True)
-    for R, Cc in (() if args.only_mlp else ((T, 768), (T, 3072))):
+    for R, Cc in (() if only else ((T, 768), (T, 3072))):
         print(json.dumps(bench_quant(R, Cc, args.iters, args.rounds)), flush=True)
-    for act in (2, 3):  # fc1 forward, fc2 data gradient: [tokens, 3072] out of K = 768
+    for act in (() if args.only_ln else (2, 3)):  # fc1 forward, fc2 data gradient: [tokens, 3072] out of K = 768
         print(json.dumps(bench_mlp(T, 3072, 768, act, args.iters, args.rounds)), flush=True)
+    for R in (() if args.only_mlp else (T, args.batch // 4 * 577)):  # 224 x 224 at the batch; 384 x 384 at a quarter
+        print(json.dumps(bench_ln(R, 768, args.iters, args.rounds)), flush=True)
 
 
 if __name__ == "__main__":
