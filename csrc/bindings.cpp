@@ -686,6 +686,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("colwise"),
         "layernorm forward with MXFP8 outputs: (stats, q, s, qt, st), the bytes of mx_quantize(layernorm_fwd(x)); "
         "qt, st None without colwise");
+  m.def("layernorm_bwd_mx", &ops::layernorm_bwd_mx, py::arg("dy"), py::arg("x"), py::arg("stats"), py::arg("w"),
+        py::arg("dres"), py::arg("dw"), py::arg("db"), py::arg("colwise"),
+        "layernorm backward that also writes dx as MXFP8: (dx, q, s, qt, st, cs_part), dx bit-equal to layernorm_bwd's, "
+        "the bytes of mx_quantize(dx) and its per-32-row-band column sums; qt, st, cs_part None without colwise");
   m.def("gemm_mxfp8", &ops::gemm_mxfp8, py::arg("a"), py::arg("sa"), py::arg("b"), py::arg("sb"), py::arg("M"),
         py::arg("N"), py::arg("K"), py::arg("out_bf16") = true, py::arg("bias") = py::none(), py::arg("act") = 0,
         py::arg("residual") = py::none(), py::arg("preact") = py::none());

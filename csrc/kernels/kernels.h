@@ -663,6 +663,16 @@ void layernorm_fwd_mx(const void* x, const float* w, const float* b, int64_t row
 int layernorm_bwd_blocks(int64_t rows);
 void layernorm_bwd(const void* dy, const void* x, const float* stats, const float* w, const void* dres, int64_t rows,
                    int D, void* dx, float* scratch, float* dw, float* db, hipStream_t s, float* cs_part = nullptr);
+// LayerNorm backward that also writes dx as MXFP8 (layernorm_bwd_mx.hip): dx is layernorm_bwd's bit for bit, and
+// q [rows][Cp], s [rows][Cp/32] and, unless qt is null, qt [D][Rp], st [D][Rp/32] are the bytes mx_quantize writes
+// for it, padding included; with qt, cs_part [layernorm_bwd_mx_bands(rows)][D] gets each 32-row band's column sums
+// of dx.  scratch holds layernorm_bwd_mx_scratch_floats floats.  D % 32 == 0, 32 <= D <= 2048; 16-B aligned rows;
+// dynamic LDS 64 * D bytes
+int layernorm_bwd_mx_bands(int64_t rows);
+int64_t layernorm_bwd_mx_scratch_floats(int64_t rows, int D);
+void layernorm_bwd_mx(const void* dy, const void* x, const float* stats, const float* w, const void* dres,
+                      int64_t rows, int D, void* dx, uint8_t* q, uint8_t* s, uint8_t* qt, uint8_t* st, float* cs_part,
+                      float* scratch, float* dw, float* db, hipStream_t stream);
 void qkv_split(const void* qkv, int B, int T, int H, int Dh, int Tp, void* q, void* k, void* v, hipStream_t s);
 void qkv_merge(const void* dq, const void* dk, const void* dv, int B, int T, int H, int Dh, int Tp, void* dqkv,
                hipStream_t s);

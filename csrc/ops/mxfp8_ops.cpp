@@ -1,4 +1,5 @@
-// Tensor-level wrappers for the MXFP8 quantiser and GEMM (csrc/kernels/mxfp8.hip, gemm_mxfp8_256.hip).
+// Tensor-level wrappers for the MXFP8 quantiser, GEMM and LayerNorms (csrc/kernels/mxfp8.hip, gemm_mxfp8_256.hip,
+// layernorm_mx.hip, layernorm_bwd_mx.hip).
 #include <c10/core/DeviceGuard.h>
 
 #include <algorithm>
@@ -101,6 +102,59 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, c10::optional<at::Tensor>, c10::o
   // must not leave the outputs unwritten without a word
   RINGDP_HIP_CHECK(hipGetLastError());
   return {stats, q, s, qt, st};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, c10::optional<at::Tensor>, c10::optional<at::Tensor>,
+           c10::optional<at::Tensor>>
+layernorm_bwd_mx(const at::Tensor& dy, const at::Tensor& x, const at::Tensor& stats, const at::Tensor& w,
+                 const c10::optional<at::Tensor>& dres, at::Tensor dw, at::Tensor db, bool colwise) {
+  bf16_gpu(dy, "layernorm_bwd_mx output grad");
+  bf16_gpu(x, "layernorm_bwd_mx input");
+  f32_gpu(stats, "layernorm_bwd_mx stats");
+  f32_gpu(w, "layernorm_bwd_mx weight");
+  f32_gpu(dw, "layernorm_bwd_mx dweight");
+  f32_gpu(db, "layernorm_bwd_mx dbias");
+  RINGDP_CHECK(x.dim() >= 1 && x.numel() >= 1, "layernorm_bwd_mx input: expected [rows >= 1, D], got ", x.sizes());
+  const int64_t D = x.size(-1), rows = x.numel() / D;
+  RINGDP_CHECK(dy.sizes() == x.sizes(), "layernorm_bwd_mx: shape mismatch");
+  RINGDP_CHECK(D % 32 == 0 && D >= 32 && D <= 2048, "layernorm_bwd_mx: expected D % 32 == 0 and 32 <= D <= 2048, got ", D);
+  RINGDP_CHECK(rows < (int64_t(1) << 31) - 128, "layernorm_bwd_mx: too many rows");
+  RINGDP_CHECK(w.numel() == D && dw.numel() == D && db.numel() == D, "layernorm_bwd_mx: w / dw / db must hold D floats");
+  RINGDP_CHECK(stats.numel() == 2 * rows, "layernorm_bwd_mx: stats must hold (mean, rstd) per row");
+  const int dev = x.get_device();
+  RINGDP_CHECK(dy.get_device() == dev && stats.get_device() == dev && w.get_device() == dev &&
+                   dw.get_device() == dev && db.get_device() == dev,
+               "layernorm_bwd_mx: tensors on different devices");
+  const void* dr = nullptr;
+  if (dres.has_value() && dres->defined()) {
+    bf16_gpu(*dres, "layernorm_bwd_mx residual grad");
+    RINGDP_CHECK(dres->sizes() == x.sizes() && dres->get_device() == dev, "layernorm_bwd_mx residual grad: shape mismatch");
+    dr = dres->data_ptr();
+  }
+  RINGDP_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(dy.data_ptr()) % 16 == 0 &&
+                   reinterpret_cast<uintptr_t>(dr) % 16 == 0,
+               "layernorm_bwd_mx: expected 16-B aligned tensors");
+  c10::DeviceGuard guard(x.device());
+  const int64_t Rp = kern::mx_pad(rows), Cp = kern::mx_pad(D);
+  const auto o = x.options().dtype(at::kByte);
+  at::Tensor dx = at::empty_like(x);
+  // (at::empty: the kernel writes every byte, padding included)
+  at::Tensor q = at::empty({rows, Cp}, o), s = at::empty({rows, Cp / 32}, o);
+  c10::optional<at::Tensor> qt, st, cs;
+  if (colwise) {
+    qt = at::empty({D, Rp}, o);
+    st = at::empty({D, Rp / 32}, o);
+    cs = at::empty({kern::layernorm_bwd_mx_bands(rows), D}, w.options());
+  }
+  at::Tensor scratch = at::empty({kern::layernorm_bwd_mx_scratch_floats(rows, (int)D)}, w.options());
+  kern::layernorm_bwd_mx(dy.data_ptr(), x.data_ptr(), stats.data_ptr<float>(), w.data_ptr<float>(), dr, rows, (int)D,
+                         dx.data_ptr(), u8(q), u8(s), colwise ? u8(*qt) : nullptr, colwise ? u8(*st) : nullptr,
+                         colwise ? cs->data_ptr<float>() : nullptr, scratch.data_ptr<float>(), dw.data_ptr<float>(),
+                         db.data_ptr<float>(), stream_of(x));
+  // 64 * D bytes of dynamic LDS (128 KiB at D = 2048): a launch the runtime refuses must not leave the outputs
+  // unwritten without a word
+  RINGDP_HIP_CHECK(hipGetLastError());
+  return {dx, q, s, qt, st, cs};
 }
 
 std::vector<at::Tensor> mx_quantize_weights(const std::vector<at::Tensor>& ws) {

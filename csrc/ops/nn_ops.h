@@ -156,6 +156,13 @@ std::vector<at::Tensor> mx_quantize_weights(const std::vector<at::Tensor>& ws); 
 // make of layernorm_fwd's bf16 output, which is never stored.  x [rows, D] bf16, D % 32 == 0, 32 <= D <= 2048
 std::tuple<at::Tensor, at::Tensor, at::Tensor, c10::optional<at::Tensor>, c10::optional<at::Tensor>> layernorm_fwd_mx(
     const at::Tensor& x, const at::Tensor& w, const at::Tensor& b, double eps, bool colwise);
+// LayerNorm backward whose dx (layernorm_bwd's bit for bit) also leaves as MXFP8 for the linear whose output gradient
+// it is: (dx, q, s, qt | None, st | None, cs_part | None), the bytes mx_quantize would make of dx and, with colwise,
+// its column sums per 32-row band [ceil(rows / 32), D].  dw / db as layernorm_bwd.  D % 32 == 0, 32 <= D <= 2048
+std::tuple<at::Tensor, at::Tensor, at::Tensor, c10::optional<at::Tensor>, c10::optional<at::Tensor>,
+           c10::optional<at::Tensor>>
+layernorm_bwd_mx(const at::Tensor& dy, const at::Tensor& x, const at::Tensor& stats, const at::Tensor& w,
+                 const c10::optional<at::Tensor>& dres, at::Tensor dw, at::Tensor db, bool colwise);
 at::Tensor gemm_mxfp8(const at::Tensor& a, const at::Tensor& sa, const at::Tensor& b, const at::Tensor& sb, int64_t M,
                       int64_t N, int64_t K, bool out_bf16, const c10::optional<at::Tensor>& bias, int64_t act,
                       const c10::optional<at::Tensor>& residual, const c10::optional<at::Tensor>& preact);

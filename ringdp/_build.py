@@ -43,6 +43,7 @@ UNIT_FLAGS = {
     "mxfp8.hip": _NO_PK_F32,
     "gemm_mxfp8_256.hip": _NO_PK_F32,
     "layernorm_mx.hip": _NO_PK_F32,
+    "layernorm_bwd_mx.hip": _NO_PK_F32,
 }
 
 

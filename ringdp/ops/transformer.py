@@ -486,6 +486,8 @@ def _linear_mx_fwd(ctx, x, w, b, residual, act, out_f32):
     ctx.shape = (M, K)
     ctx.params = (w, b)
     ctx.cfg = (act, residual is not None, N)
+    if act == 0 and not out_f32:
+        y._ringdp_mx_dz = want_dw  # y's gradient is this linear's dz: see _ln_bwd_mx
     return y
 
 
@@ -494,11 +496,16 @@ def _linear_mx_bwd(ctx, dy):
     w, b = ctx.params
     act, has_res, N = ctx.cfg
     M, K = ctx.shape
+    want_dx, want_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    # dz as MXFP8 and its column sums from the kernel that produced dy (a LayerNorm or attention backward)
+    dz_mx = _mx_grad_of(dy, M, N, want_dw) if act == 0 else None
+    part = _mx_colsum_of(dy, N) if act == 0 else None
     dyb = dy.contiguous() if dy.dtype == torch.bfloat16 else _bf16(dy)
     dz = C.gelu_bwd(dyb, pre) if act == 2 else dyb
-    want_dx, want_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
     dx = dw = db = None
-    if want_dx or want_dw:
+    if dz_mx is not None:
+        dzq, dzs, dzqt, dzst = dz_mx
+    elif want_dx or want_dw:
         dzq, dzs, dzqt, dzst = C.mx_quantize(dz, want_dx, want_dw)  # blocks along N for dx, along M for dW
     if want_dx:  # dx[m][k] = sum_n dz[m][n] W[n][k]: W column-wise, i.e. W^T blocked along n
         dx = C.gemm_mxfp8(dzq, dzs, wqt, wst, M, K, dzq.shape[1], True)
@@ -508,9 +515,54 @@ def _linear_mx_bwd(ctx, dy):
         C.gemm_mxfp8_splitk_f32(dzqt, dzst, xqt, xst, N, K, dzqt.shape[1], _splits(M, N, K), dw)
     if b is not None and ctx.needs_input_grad[2]:
         db = grad_buffer(b)
-        C.colsum_f32(dz, db)
+        if part is not None:
+            C.rowsum_f32(part, db)
+        else:
+            C.colsum_f32(dz, db)
     dres = dyb if has_res and ctx.needs_input_grad[3] else None
     return dx, dw, db, dres, None, None
+
+
+# MXFP8 recipe: the LayerNorm backward whose dx is the output gradient of an MXFP8 linear (attention proj / fc2 behind
+# ln_2 / the next ln_1 / the final LayerNorm) writes that dx as MXFP8 and as per-band column sums too, and the
+# attention backward hands its per-batch column sums to the qkv projection, so the linear's backward runs neither
+# mx_quantize nor colsum_f32 (RINGDP_MX_LN_BWD_FUSED=0: those passes, for A/B runs)
+_MX_LN_BWD_FUSED = os.environ.get("RINGDP_MX_LN_BWD_FUSED", "1") != "0"
+
+
+def _mx_stamp(dx) -> None:
+    """Marks what is attached to the gradient ``dx`` as describing its present values: autograd may add a second
+    gradient into ``dx`` in place (a tensor with two consumers) and the Python attributes survive that, but the
+    tensor's version does not."""
+    dx._ringdp_mx_ver = dx._version
+
+
+def _mx_fresh(dy) -> bool:
+    return getattr(dy, "_ringdp_mx_ver", None) == dy._version
+
+
+def _mx_colsum_of(dy, N: int):
+    """The column-sum partials [., N] attached to the gradient ``dy`` (``_ringdp_colsum_part``), or None: none
+    attached, other shapes, or ``dy`` was written since (see _mx_stamp)."""
+    part = getattr(dy, "_ringdp_colsum_part", None)
+    return part if part is not None and _mx_fresh(dy) and part.dim() == 2 and part.shape[1] == N else None
+
+
+def _mx_grad_of(dy, M: int, N: int, need_t: bool):
+    """(q, s, qt, st) that the producer of the gradient ``dy`` [M, N] attached to it (``_ringdp_mx``, see
+    _ln_bwd_mx), or None: no attribute (a hook replaced the tensor, autograd summed into a new one), ``dy`` written
+    since they were attached (autograd summed into it in place, see _mx_stamp), other shapes, or no column-wise
+    bytes although the weight gradient is wanted."""
+    e = getattr(dy, "_ringdp_mx", None)
+    if e is None or not _mx_fresh(dy) or tuple(dy.shape) != (M, N):
+        return None
+    q, s, qt, st = e
+    Mp, Np = (M + 127) // 128 * 128, (N + 127) // 128 * 128
+    if tuple(q.shape) != (M, Np) or tuple(s.shape) != (M, Np // 32):
+        return None
+    if need_t and (qt is None or st is None or tuple(qt.shape) != (N, Mp) or tuple(st.shape) != (N, Mp // 32)):
+        return None
+    return e
 
 
 # MXFP8 recipe: the MLP's [tokens, hidden] tensors leave their GEMM epilogues as MXFP8 (RINGDP_MX_MLP_FUSED=0: the
@@ -549,6 +601,7 @@ class MLPMX(torch.autograd.Function):
         ctx.params = (w1, b1, w2, b2)
         ctx.dims = (M, D, Hd)
         ctx.has_res = residual is not None
+        y._ringdp_mx_dz = ctx.needs_input_grad[3]  # y's gradient is fc2's dz: see _ln_bwd_mx
         return y
 
     @staticmethod
@@ -557,12 +610,20 @@ class MLPMX(torch.autograd.Function):
         w1, b1, w2, b2 = ctx.params
         M, D, Hd = ctx.dims
         n = ctx.needs_input_grad
+        dy_mx = _mx_grad_of(dy, M, D, n[3])  # from the LayerNorm backward that produced dy
+        part = _mx_colsum_of(dy, D)
         dyb = dy.contiguous() if dy.dtype == torch.bfloat16 else _bf16(dy)
-        dyq, dys, dyqt, dyst = C.mx_quantize(dyb, True, True)  # blocks along D for dz1, along the tokens for dW2
+        if dy_mx is not None:
+            dyq, dys, dyqt, dyst = dy_mx
+        else:
+            dyq, dys, dyqt, dyst = C.mx_quantize(dyb, True, True)  # blocks along D for dz1, along the tokens for dW2
         db2 = None
         if n[4]:
             db2 = grad_buffer(b2)
-            C.colsum_f32(dyb, db2)
+            if part is not None:
+                C.rowsum_f32(part, db2)
+            else:
+                C.colsum_f32(dyb, db2)
         dw2 = None
         if n[3]:  # dW2[d][j] = sum_m dy[m][d] a[m][j]
             dw2 = grad_buffer(w2)
@@ -645,6 +706,7 @@ class LayerNormFork(torch.autograd.Function):
         y, stats = C.layernorm_fwd(x, w, b, eps)
         ctx.save_for_backward(x, stats)
         ctx.params = (w, b)
+        ctx.mx_dz = getattr(x, "_ringdp_mx_dz", None)
         return y, x
 
     @staticmethod
@@ -655,7 +717,9 @@ class LayerNormFork(torch.autograd.Function):
             return dres, None, None, None
         dw, db = grad_buffer(w), grad_buffer(b)
         res = dres.contiguous() if dres is not None else None
-        if _FP8["on"] or not _LN_COLSUM:  # (fp8 linears take their bias gradients from the quantisation pass)
+        if _ln_bwd_mx_ok(ctx, x):
+            dx = _ln_bwd_mx(ctx, dy.contiguous(), x, stats, w, res, dw, db)
+        elif _FP8["on"] or not _LN_COLSUM:  # (fp8 linears take their bias gradients from the quantisation pass)
             dx = C.layernorm_bwd(dy.contiguous(), x, stats, w, res, dw, db)
         else:
             # dx is the output gradient of the linear that produced x (attention proj / fc2, residual fused):
@@ -663,6 +727,26 @@ class LayerNormFork(torch.autograd.Function):
             dx, part = C.layernorm_bwd_colsum(dy.contiguous(), x, stats, w, res, dw, db)
             dx._ringdp_colsum_part = part
         return dx, dw, db, None
+
+
+def _ln_bwd_mx_ok(ctx, x) -> bool:
+    """The LayerNorm's input came from an MXFP8 linear whose dz is this backward's dx (the forward kept the linear's
+    mark, ``_ringdp_mx_dz``), within layernorm_bwd_mx's shapes.  Block 0's ln_1, a LayerNorm behind dropout and every
+    model outside the MXFP8 recipe carry no mark and launch nothing new."""
+    d = x.shape[-1]
+    return getattr(ctx, "mx_dz", None) is not None and _FP8["mx"] and _MX_LN_BWD_FUSED and x.dim() == 2 \
+        and x.is_contiguous() and x.dtype == torch.bfloat16 and d % 32 == 0 and d <= 2048
+
+
+def _ln_bwd_mx(ctx, dy, x, stats, w, res, dw, db):
+    """layernorm_bwd_mx: dx (layernorm_bwd's bits) carries its own MXFP8 bytes - column-wise too if the linear's
+    weight gradient is wanted - and per-band column sums, which _linear_mx_bwd / MLPMX.backward read from it."""
+    dx, q, s, qt, st, part = C.layernorm_bwd_mx(dy, x, stats, w, res, dw, db, bool(ctx.mx_dz))
+    dx._ringdp_mx = (q, s, qt, st)
+    if part is not None:
+        dx._ringdp_colsum_part = part
+    _mx_stamp(dx)
+    return dx
 
 
 _FP8_LN_Q8 = os.environ.get("RINGDP_FP8_LN_Q8", "1") == "1"
@@ -727,6 +811,7 @@ class LayerNormForkMX(torch.autograd.Function):
         stats, q, s, qt, st = C.layernorm_fwd_mx(x, w, b, eps, colwise)
         ctx.save_for_backward(x, stats)
         ctx.params = (w, b)
+        ctx.mx_dz = getattr(x, "_ringdp_mx_dz", None)
         y = torch.empty_like(x)
         y._ringdp_mx = (q, s, qt, st)
         return y, x
@@ -785,6 +870,7 @@ class LayerNormF(torch.autograd.Function):
         y, stats = C.layernorm_fwd(x, w, b, eps)
         ctx.save_for_backward(x, stats)
         ctx.params = (w, b)
+        ctx.mx_dz = getattr(x, "_ringdp_mx_dz", None)
         return y
 
     @staticmethod
@@ -792,7 +878,10 @@ class LayerNormF(torch.autograd.Function):
         x, stats = ctx.saved_tensors
         w, b = ctx.params
         dw, db = grad_buffer(w), grad_buffer(b)
-        dx = C.layernorm_bwd(dy.contiguous(), x, stats, w, None, dw, db)
+        if _ln_bwd_mx_ok(ctx, x):
+            dx = _ln_bwd_mx(ctx, dy.contiguous(), x, stats, w, None, dw, db)
+        else:
+            dx = C.layernorm_bwd(dy.contiguous(), x, stats, w, None, dw, db)
         return dx, dw, db, None
 
 
@@ -842,13 +931,14 @@ class AttentionF(torch.autograd.Function):
             qkv, p, *rest = ctx.saved_tensors
             out = rest[0] if rest else None  # saved for Tp > 256 only
             B, T, H, Tp, scale = ctx.cfg
-            if p.dtype == torch.float32 and not _FP8["on"]:
+            if p.dtype == torch.float32 and (not _FP8["on"] or (_FP8["mx"] and _MX_LN_BWD_FUSED)):
                 # the kernels also sum their dq / dk / dv rows per batch (per batch and 64-row block for
                 # Tp > 256): the qkv projection's bias gradient is then one [rows, 3D] -> [3D] reduction in
                 # LinearF's backward instead of a pass over dqkv
                 part = torch.empty(C.attn_colsum_rows(B, T), qkv.shape[1], device=qkv.device, dtype=torch.float32)
                 dqkv = C.attn_bwd_rows(dout.contiguous(), qkv, p, B, T, H, scale, part, out)
                 dqkv._ringdp_colsum_part = part
+                _mx_stamp(dqkv)  # (read by the MXFP8 linear only; the bf16 LinearF takes the partials as before)
                 return dqkv, None, None, None
             return C.attn_bwd_rows(dout.contiguous(), qkv, p, B, T, H, scale, None, out), None, None, None
         q, k, v, p = ctx.saved_tensors

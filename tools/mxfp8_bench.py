@@ -6,7 +6,8 @@ Quantiser: ``mx_quantize`` (both orientations) vs ``fp8_quantize_both_delayed`` 
 [tokens, 3072] activations, as GB/s of the bytes each must move (one bf16 read, two e4m3 writes, plus MX scales).
 MLP epilogue: ``gemm_mxfp8_quant_out`` on the two [tokens, 3072] x 768 MLP GEMMs (act 2 and act 3) vs the passes it
 replaces and vs the GEMM alone.
-LayerNorm: ``layernorm_fwd_mx`` vs ``layernorm_fwd`` + ``mx_quantize`` at [128 x 197, 768] and [32 x 577, 768].
+LayerNorm: ``layernorm_fwd_mx`` vs ``layernorm_fwd`` + ``mx_quantize``, and ``layernorm_bwd_mx`` vs ``layernorm_bwd`` +
+``mx_quantize`` + ``colsum_f32`` (and vs ``layernorm_bwd`` alone), at [128 x 197, 768] and [32 x 577, 768].
 The variants of a row are timed alternately, ``--rounds`` windows each; the median and the spread are printed.
 One JSON line per row.
 """
@@ -147,6 +148,38 @@ def bench_ln(R: int, D: int, iters: int, rounds: int) -> dict:
             "fused_gbs": round(byt / m / 1e6, 1), "passes_gbs": round((byt + R * D * 4) / p / 1e6, 1)}
 
 
+def bench_ln_bwd(R: int, D: int, iters: int, rounds: int) -> dict:
+    """``layernorm_bwd_mx`` (both orientations, band column sums) against the three calls it replaces,
+    ``layernorm_bwd``, ``mx_quantize`` and ``colsum_f32`` of its dx, and against ``layernorm_bwd`` alone (what the
+    MXFP8 outputs cost on top), in alternating windows."""
+    x, dy, dres = (torch.randn(R, D, device="cuda").bfloat16() for _ in range(3))
+    w = torch.rand(D, device="cuda") + 0.5
+    stats = C.layernorm_fwd(x, w, torch.zeros_like(w), 1e-6)[1]
+    dw, db, cs = (torch.empty(D, device="cuda") for _ in range(3))
+
+    def passes():
+        dx = C.layernorm_bwd(dy, x, stats, w, dres, dw, db)
+        C.mx_quantize(dx, True, True)
+        C.colsum_f32(dx, cs)
+
+    fns = {"fused": lambda: C.layernorm_bwd_mx(dy, x, stats, w, dres, dw, db, True), "passes": passes,
+           "bwd_only": lambda: C.layernorm_bwd(dy, x, stats, w, dres, dw, db)}
+    for f in fns.values():
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    ts = {k: [] for k in fns}
+    for _ in range(rounds):  # alternating windows
+        for k, f in fns.items():
+            ts[k].append(_time(f, iters))
+    out = {"kind": "layernorm_bwd", "R": R, "D": D}
+    for k, v in ts.items():
+        m, lo, hi = _stats(v)
+        out[k + "_ms"] = round(m, 4)
+        out[k + "_ms_range"] = [round(lo, 4), round(hi, 4)]
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--batch", type=int, default=128, help="images per step (197 tokens each)")
@@ -172,6 +205,7 @@ def main() -> None:
         print(json.dumps(bench_mlp(T, 3072, 768, act, args.iters, args.rounds)), flush=True)
     for R in (() if args.only_mlp else (T, args.batch // 4 * 577)):  # 224 x 224 at the batch; 384 x 384 at a quarter
         print(json.dumps(bench_ln(R, 768, args.iters, args.rounds)), flush=True)
+        print(json.dumps(bench_ln_bwd(R, 768, args.iters, args.rounds)), flush=True)
 
 
 if __name__ == "__main__":
