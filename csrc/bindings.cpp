@@ -650,6 +650,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("colsum_part") = py::none(), py::arg("out") = py::none(), py::arg("force_long") = false);
   m.def("attn_colsum_rows", &ops::attn_colsum_rows, "rows of attn_bwd_rows' colsum_part", py::arg("B"), py::arg("T"),
         py::arg("force_long") = false);
+  m.def("attn_drop_fwd_rows", &ops::attn_drop_fwd_rows,
+        "fused attention forward with dropout on the probabilities (head dim 64, any T; thr8 = round(p * 256) in "
+        "1 .. 255): returns [log-sum-exp of the undropped softmax, out rows [B*T, H*64]]",
+        py::arg("qkv"), py::arg("B"), py::arg("T"), py::arg("H"), py::arg("scale"), py::arg("snapshot"),
+        py::arg("site"), py::arg("thr8"));
+  m.def("attn_drop_bwd_rows", &ops::attn_drop_bwd_rows,
+        "backward of attn_drop_fwd_rows -> dqkv rows (the mask is regenerated from snapshot and site); colsum_part "
+        "is [attn_colsum_rows(B, T, force_long=True), 3*H*64]",
+        py::arg("dout"), py::arg("qkv"), py::arg("lse"), py::arg("out"), py::arg("B"), py::arg("T"), py::arg("H"),
+        py::arg("scale"), py::arg("snapshot"), py::arg("site"), py::arg("thr8"), py::arg("colsum_part") = py::none());
   m.def("rowsum_f32", &ops::rowsum_f32, "out[c] = sum_r part[r][c] (fp32, fixed order)");
   m.def("attn_bwd", &ops::attn_bwd,
         "fused attention backward -> dqkv rows [B*T, 3*H*Dh] (query-side dQ kernel + key-side dK/dV kernel)");

@@ -734,6 +734,17 @@ void rng_tick(uint64_t* state, uint64_t* snapshot, hipStream_t s);
 //   res != nullptr:  y = m ? bf16(res + m * x) : res
 void dropout_bf16(const void* x, const void* res, const uint64_t* snapshot, uint32_t site_e, uint32_t thr_e,
                   uint32_t site_r, uint32_t thr_r, int64_t row_elems, int64_t n, void* y, hipStream_t s);
+// Dropout on the attention probabilities inside the key-blocked attention kernels (vit_attn_drop.hip; head dim
+// 64, any T, Tp = T rounded up to 16): O = (keep ? 256 / (256 - thr8) P : 0) V with one Philox call per 4 x 4 tile
+// of (query, key) pairs, group = ((b H + h) N4 + tq / 4) N4 + tk / 4, N4 = ceil(T / 4), 8-bit draws (byte tk & 3 of
+// word tq & 3), keep iff draw >= thr8.  lse is that of the undropped softmax; the backward regenerates the mask.
+// Operands, dsum and colsum_part as attn_fwd_rows_long / attn_bwd_rows_long.  false = unsupported: head dim != 64,
+// thr8 outside 1 .. 255, no snapshot, or B H N4 N4 > 2^32.
+bool attn_drop_fwd_rows(const void* qkv, int B, int T, int H, int Tp, int Dh, float scale, const uint64_t* snapshot,
+                        uint32_t site, uint32_t thr8, float* lse, void* out, hipStream_t s);
+bool attn_drop_bwd_rows(const void* dout_rows, const void* qkv, const float* lse, const void* out_rows, int B, int T,
+                        int H, int Tp, int Dh, float scale, const uint64_t* snapshot, uint32_t site, uint32_t thr8,
+                        float* dsum, void* dqkv, hipStream_t s, float* colsum_part = nullptr);
 
 // ---------------------------------------------------------------- mixup / cutmix (mixup.hip)
 // Records: int32 [R, 8] = {lam (fp32 bits), kind (0 not applied, 1 mixup, 2 cutmix), y0, y1, x0, x1, lam0 (fp32

@@ -1,6 +1,6 @@
 // Shared pieces of the fused attention kernels (head dim 64): the strided operand views, the LDS swizzles and
-// the column-sum epilogue.  Used by vit.hip (Tp <= 256: all of K and V of a head in LDS) and by
-// vit_attn_long.hip (any length: key-blocked).
+// the column-sum epilogue.  Used by vit.hip (Tp <= 256: all of K and V of a head in LDS), by
+// vit_attn_long.hip (any length: key-blocked) and by vit_attn_drop.hip (key-blocked, dropout on P).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -40,6 +40,22 @@ struct AttnOut {
 __device__ __forceinline__ int att_ksw(int r, int d) { return r * ATT_D + ((((d >> 3) ^ (r & 7))) << 3) + (d & 7); }
 __device__ __forceinline__ int att_vsw(int r, int d) {
   return r * ATT_D + ((((d >> 4) ^ ((r >> 1) & 3))) << 4) + (d & 15);
+}
+
+// Key-blocked kernels (vit_attn_long.hip, vit_attn_drop.hip)
+constexpr int ATTL_KB = 128;            // rows per staged block: 2 x 16 KiB of LDS, 32 score registers
+constexpr int ATTL_NT = ATTL_KB / 16;   // 16-row tiles per block
+constexpr int ATTL_WG = 64;             // rows owned by a workgroup: one 16-row tile per wave
+
+// stage rows r0 .. r0 + ATTL_KB of two operands into LDS (rows >= T zero), each with its own swizzle
+template <bool A_KSW, bool B_KSW>
+__device__ __forceinline__ void attl_stage(const AttnIn& a, const AttnIn& b, bf16* As, bf16* Bs, int bh, int H, int r0,
+                                           int T) {
+  for (int c = threadIdx.x; c < ATTL_KB * 8; c += 256) {  // 16-B chunks: row c >> 3, columns 8 (c & 7) ..
+    const int r = c >> 3, d = (c & 7) * 8;
+    *reinterpret_cast<bf16x8*>(As + (A_KSW ? att_ksw(r, d) : att_vsw(r, d))) = a.load8(bh, H, r0 + r, T, d);
+    *reinterpret_cast<bf16x8*>(Bs + (B_KSW ? att_ksw(r, d) : att_vsw(r, d))) = b.load8(bh, H, r0 + r, T, d);
+  }
 }
 
 // Column sums of a kernel's 64-wide output block (a bias gradient's partial): lane (g, i) holds sums for columns

@@ -23,21 +23,6 @@ using namespace ringdp::dev;
 
 namespace {
 
-constexpr int ATTL_KB = 128;            // rows per staged block: 2 x 16 KiB of LDS, 32 score registers
-constexpr int ATTL_NT = ATTL_KB / 16;   // 16-row tiles per block
-constexpr int ATTL_WG = 64;             // rows owned by a workgroup: one 16-row tile per wave
-
-// stage rows r0 .. r0 + ATTL_KB of two operands into LDS (rows >= T zero), each with its own swizzle
-template <bool A_KSW, bool B_KSW>
-__device__ __forceinline__ void attl_stage(const AttnIn& a, const AttnIn& b, bf16* As, bf16* Bs, int bh, int H, int r0,
-                                           int T) {
-  for (int c = threadIdx.x; c < ATTL_KB * 8; c += 256) {  // 16-B chunks: row c >> 3, columns 8 (c & 7) ..
-    const int r = c >> 3, d = (c & 7) * 8;
-    *reinterpret_cast<bf16x8*>(As + (A_KSW ? att_ksw(r, d) : att_vsw(r, d))) = a.load8(bh, H, r0 + r, T, d);
-    *reinterpret_cast<bf16x8*>(Bs + (B_KSW ? att_ksw(r, d) : att_vsw(r, d))) = b.load8(bh, H, r0 + r, T, d);
-  }
-}
-
 // Forward.  Per key block: S^T = K Q^T into ATTL_NT f32x4 (lane (g, q): keys k0 + 16t + 4g + i of query
 // q = lane & 15), block maximum, m_new = max(m, block max), one per-lane factor exp2((m - m_new) c) on the 16
 // accumulator registers and the running sum (every element of a lane belongs to query lane & 15), then

@@ -66,7 +66,69 @@ at::Tensor run(const at::Tensor& x, const at::Tensor* res, const c10::optional<a
   return y;
 }
 
+// the checks the two attention-dropout ops share; returns the snapshot's device pointer
+const uint64_t* check_attn_drop(const at::Tensor& qkv, int64_t B, int64_t T, int64_t H,
+                                const c10::optional<at::Tensor>& snap, int64_t site, int64_t thr8, const char* name) {
+  bf16_gpu(qkv, "attention qkv rows");
+  RINGDP_CHECK(B > 0 && T > 0 && H > 0 && qkv.dim() == 2 && qkv.size(0) == B * T && qkv.size(1) % (3 * H) == 0, name,
+               ": qkv [B*T, 3*H*Dh]");
+  RINGDP_CHECK(qkv.size(1) == 3 * H * 64, name, ": attention dropout needs head dim 64, got ", qkv.size(1) / (3 * H));
+  RINGDP_CHECK(thr8 >= 1 && thr8 <= 255, name, ": thr8 = round(p * 256) must be in [1, 255], got ", thr8,
+               " (0 is the identity: call attn_fwd_rows)");
+  RINGDP_CHECK(site >= 0 && site <= 0xffffffffLL, name, ": site id out of range: ", site);
+  RINGDP_CHECK(snap.has_value() && snap->defined(), name, ": a snapshot (rng_tick) is needed");
+  check_rng_pair(*snap, "attention dropout snapshot");
+  RINGDP_CHECK(snap->get_device() == qkv.get_device(), name, ": snapshot on another device");
+  const int64_t N4 = (T + 3) / 4;
+  RINGDP_CHECK(B * H * N4 <= (int64_t(1) << 32) / N4, name, ": B*H*ceil(T/4)^2 = ", B * H * N4, " * ", N4,
+               " mask tiles do not fit the 32-bit group counter");
+  return reinterpret_cast<const uint64_t*>(snap->data_ptr<int64_t>());
+}
+
 }  // namespace
+
+std::vector<at::Tensor> attn_drop_fwd_rows(const at::Tensor& qkv, int64_t B, int64_t T, int64_t H, double scale,
+                                           const c10::optional<at::Tensor>& snapshot, int64_t site, int64_t thr8) {
+  const uint64_t* snap = check_attn_drop(qkv, B, T, H, snapshot, site, thr8, "attn_drop_fwd_rows");
+  const int64_t Tp = (T + 15) / 16 * 16;
+  c10::DeviceGuard guard(qkv.device());
+  at::Tensor out = at::empty({B * T, H * 64}, qkv.options());
+  at::Tensor lse = at::empty({B * H, Tp}, qkv.options().dtype(at::kFloat));
+  const bool ok = kern::attn_drop_fwd_rows(qkv.data_ptr(), (int)B, (int)T, (int)H, (int)Tp, 64, (float)scale, snap,
+                                           (uint32_t)site, (uint32_t)thr8, lse.data_ptr<float>(), out.data_ptr(),
+                                           stream_of(qkv));
+  RINGDP_CHECK(ok, "attn_drop_fwd_rows: unsupported shape");
+  return {lse, out};
+}
+
+at::Tensor attn_drop_bwd_rows(const at::Tensor& dout, const at::Tensor& qkv, const at::Tensor& lse,
+                              const at::Tensor& out, int64_t B, int64_t T, int64_t H, double scale,
+                              const c10::optional<at::Tensor>& snapshot, int64_t site, int64_t thr8,
+                              const c10::optional<at::Tensor>& colsum_part) {
+  const uint64_t* snap = check_attn_drop(qkv, B, T, H, snapshot, site, thr8, "attn_drop_bwd_rows");
+  const int64_t Tp = (T + 15) / 16 * 16;
+  bf16_gpu(dout, "attention output grad rows");
+  bf16_gpu(out, "attention output rows");
+  f32_gpu(lse, "attention log-sum-exp");
+  RINGDP_CHECK(dout.dim() == 2 && dout.size(0) == B * T && dout.size(1) == H * 64 && out.sizes() == dout.sizes() &&
+                   lse.dim() == 2 && lse.size(0) == B * H && lse.size(1) == Tp,
+               "attn_drop_bwd_rows: shape mismatch (dout, out [B*T, H*64]; lse [B*H, Tp])");
+  float* csp = nullptr;
+  if (colsum_part.has_value() && colsum_part->defined()) {  // every entry is written by one workgroup
+    f32_gpu(*colsum_part, "attention dqkv column-sum partials");
+    RINGDP_CHECK(colsum_part->numel() == attn_colsum_rows(B, T, true) * qkv.size(1) && colsum_part->is_contiguous(),
+                 "attn_drop_bwd_rows: colsum_part must be [attn_colsum_rows(B, T, force_long=True), 3*H*64] floats");
+    csp = colsum_part->data_ptr<float>();
+  }
+  c10::DeviceGuard guard(qkv.device());
+  at::Tensor dqkv = at::empty_like(qkv);
+  at::Tensor dsum = at::empty({B * H, Tp}, qkv.options().dtype(at::kFloat));
+  const bool ok = kern::attn_drop_bwd_rows(dout.data_ptr(), qkv.data_ptr(), lse.data_ptr<float>(), out.data_ptr(),
+                                           (int)B, (int)T, (int)H, (int)Tp, 64, (float)scale, snap, (uint32_t)site,
+                                           (uint32_t)thr8, dsum.data_ptr<float>(), dqkv.data_ptr(), stream_of(qkv), csp);
+  RINGDP_CHECK(ok, "attn_drop_bwd_rows: unsupported shape");
+  return dqkv;
+}
 
 at::Tensor rng_tick(at::Tensor state) {
   check_rng_pair(state, "rng state");

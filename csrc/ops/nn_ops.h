@@ -59,6 +59,15 @@ at::Tensor dropout_bf16(const at::Tensor& x, const c10::optional<at::Tensor>& sn
                         int64_t site_r, int64_t thr_r, int64_t T);
 at::Tensor dropout_add_bf16(const at::Tensor& x, const at::Tensor& res, const c10::optional<at::Tensor>& snapshot,
                             int64_t site_e, int64_t thr_e, int64_t site_r, int64_t thr_r, int64_t T);
+// Fused attention with dropout on the probabilities (vit_attn_drop.hip; head dim 64, any T): thr8 = round(p * 256)
+// in 1 .. 255.  Forward: [log-sum-exp of the undropped softmax [B*H, Tp], out rows]; the backward takes both and
+// colsum_part [attn_colsum_rows(B, T, force_long=true), 3*H*64].
+std::vector<at::Tensor> attn_drop_fwd_rows(const at::Tensor& qkv, int64_t B, int64_t T, int64_t H, double scale,
+                                           const c10::optional<at::Tensor>& snapshot, int64_t site, int64_t thr8);
+at::Tensor attn_drop_bwd_rows(const at::Tensor& dout, const at::Tensor& qkv, const at::Tensor& lse,
+                              const at::Tensor& out, int64_t B, int64_t T, int64_t H, double scale,
+                              const c10::optional<at::Tensor>& snapshot, int64_t site, int64_t thr8,
+                              const c10::optional<at::Tensor>& colsum_part = c10::nullopt);
 
 // Mixup / CutMix (mixup_ops.cpp).  mix_draw: int32 [R, 8] records {lam, kind, y0, y1, x0, x1, lam0, 0} drawn from an
 // rng_tick snapshot, R = 1 (per batch) or B (per sample).  mix_images: (x mixed with x.flip(0), y.flip(0)) for

@@ -15,7 +15,8 @@ it - after tokens + position embedding, after GELU, and on each residual branch 
 drop-path, per-layer probability ``p * l / (L - 1)``) drops both residual branches of a block per sample.  On the
 GPU the masks come from ``ringdp.ops.dropout`` (one ``rng_tick`` per forward, hipGraph-safe), the residual add,
 the dropout and the drop-path of a branch are one kernel, and the block takes the unfused linears instead of
-MLPF / MLPF8, which costs the separate GELU-backward pass.  With everything at 0, or in ``eval()``, the path and
+MLPF / MLPF8, which costs the separate GELU-backward pass.  ``attention_dropout`` drops attention probabilities
+inside the fused attention kernels (``vit_attn_drop.hip``, head dim 64; another head dim raises).  With everything at 0, or in ``eval()``, the path and
 the launches are the ones described above.
 
 Fine-tuning at another resolution: ``load_state_dict(sd, resize_pos_embedding=True)`` resizes the checkpoint's
@@ -30,7 +31,7 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 
-from ..ops.dropout import DropoutF, drop_path_rows, drop_path_schedule, dropout_add, quantize_p
+from ..ops.dropout import DropoutF, drop_path_rows, drop_path_schedule, dropout_add, quantize_p, quantize_p8
 from ..ops.transformer import (AttentionF, ClassRowsF, LayerNormF, LayerNormFork, MLPF, MLPF8, MLPMX, PatchTokensF,
                                 cast_weights, clear_weights, fp8_enabled, fp8_mlp_fusable, layernorm_fork, linear,
                                 mx_mlp_fusable)
@@ -72,26 +73,30 @@ class EncoderBlock(nn.Module):
         """Whether forward_rows takes the dropout path: decided on the quantised thresholds the kernels use, so a
         probability too small to drop anything (below 2^-17) keeps the fused path."""
         return self.training and bool(quantize_p(self.dropout.p)[0] or quantize_p(self.drop_path)[0]
-                                      or self.self_attention.dropout > 0.0)
+                                      or quantize_p8(self.self_attention.dropout)[0])
 
     def forward_rows_dropout(self, x, B: int, T: int, draw=None):
         """The training path with dropout and / or stochastic depth: unfused linears with the residual add, the
-        dropout and the drop-path of each branch in one kernel (DropoutAddF).  Sites in call order: out-proj
-        branch (element, then row), GELU output, fc2 branch (element, then row); a factor that is off takes no
-        site.  ``draw``: the forward's ``ringdp.random.Draw``; a block called on its own makes one."""
+        dropout and the drop-path of each branch in one kernel (DropoutAddF); attention dropout runs inside the
+        fused attention kernels (head dim 64).  Sites in call order: attention probabilities, out-proj branch
+        (element, then row), GELU output, fc2 branch (element, then row); a factor that is off takes no site.
+        ``draw``: the forward's ``ringdp.random.Draw``; a block called on its own makes one."""
         att = self.self_attention
-        if att.dropout > 0.0:
-            raise NotImplementedError("EncoderBlock: attention_dropout > 0 is not supported on the GPU path "
-                                      "(the fused attention kernels have no dropout)")
         p, dp = self.dropout.p, self.drop_path
-        thr = quantize_p(p)[0]
-        if draw is None and (thr or quantize_p(dp)[0]):
+        thr, thr8 = quantize_p(p)[0], quantize_p8(att.dropout)[0]
+        if thr8 and att.head_dim != 64:
+            raise NotImplementedError("EncoderBlock: attention_dropout > 0 on the GPU path needs head dim 64, got "
+                                      f"{att.head_dim} (the fused attention kernels with dropout are head dim 64 only)")
+        if draw is None and (thr or thr8 or quantize_p(dp)[0]):
             draw = Draw(x.device)
         fc1, fc2 = self.mlp[0], self.mlp[3]
         # layernorm_fork: LayerNormFork on the bf16 path, the e4m3-writing fork for fp8 linears
         h, x = layernorm_fork(x, self.ln_1, att.in_proj_weight)
         qkv = _lin(h, att.in_proj_weight, att.in_proj_bias)
-        o = AttentionF.apply(qkv, B, T, self.num_heads)
+        if thr8:
+            o = AttentionF.apply(qkv, B, T, self.num_heads, draw.snapshot, draw.site(), thr8)
+        else:
+            o = AttentionF.apply(qkv, B, T, self.num_heads)
         h = linear(o, att.out_proj)  # no residual in the epilogue
         x = dropout_add(h, x, p, True, draw, dp, T)
         h, x = layernorm_fork(x, self.ln_2, fc1.weight)

@@ -12,6 +12,17 @@ Mask definition (what the kernels compute, bit for bit; ``tests/dropout_common.p
 * ``thr = clamp(round(p * 65536), 0, 65535)``; keep iff ``u16 >= thr``; ``scale = 65536 / (65536 - thr)`` (fp32):
   the exact inverse of the realised keep probability, so the expectation is unbiased.  ``thr == 0`` is the
   identity and launches nothing.
+* attention mode (dropout on the attention probabilities, inside the fused attention kernels of
+  ``csrc/kernels/vit_attn_drop.hip``; one ``site`` per attention call)  one call covers a 4 x 4 tile of (query, key)
+  pairs of one (batch, head) with 8-bit draws: for batch ``b``, head ``h``, query ``tq`` and key ``tk`` (all
+  ``< T``) and ``N4 = ceil(T / 4)``, ``g = ((b*H + h) * N4 + (tq >> 2)) * N4 + (tk >> 2)`` and the draw is
+  ``(word[tq & 3] >> (8 * (tk & 3))) & 0xff``; ``B*H*N4*N4 <= 2^32`` is checked.
+  ``thr8 = clamp(round(p * 256), 0, 255)``; keep iff ``u8 >= thr8``; ``scale_keep = 256 / (256 - thr8)`` (fp32), the
+  exact inverse of the realised keep probability; ``thr8 == 0`` is the identity, takes no site and launches the
+  kernels without dropout.  With ``P = softmax(scale Q K^T)`` over the ``T`` real keys:
+  ``Pd = keep ? scale_keep * P : 0``, ``O = Pd V``; the saved log-sum-exp is that of the undropped softmax.
+  Backward: ``dPd = dO V^T``, ``dP = keep ? scale_keep * dPd : 0``, ``D = rowsum(dO * O)`` (``= rowsum(dP * P)``),
+  ``dS = scale * P * (dP - D)``, ``dV = Pd^T dO``, ``dK = dS^T Q``, ``dQ = dS K``.
 
 No mask is stored: the backward regenerates it (``dx = dropout(dy)`` with the same snapshot and site).
 """
@@ -34,6 +45,17 @@ def quantize_p(p: float) -> Tuple[int, float]:
     thr = min(max(int(round(p * 65536.0)), 0), 65535)
     scale = struct.unpack("f", struct.pack("f", 65536.0 / (65536 - thr)))[0]
     return thr, scale
+
+
+def quantize_p8(p: float) -> Tuple[int, float]:
+    """``(thr8, scale_keep)`` of an attention-dropout probability: 8-bit threshold and the fp32 scale of the kept
+    probabilities (attention mode above)."""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"dropout probability has to be between 0 and 1, but got {p}")
+    thr8 = min(max(int(round(p * 256.0)), 0), 255)
+    scale = struct.unpack("f", struct.pack("f", 256.0 / (256 - thr8)))[0]
+    return thr8, scale
 
 
 def drop_path_schedule(p: float, num_layers: int):

@@ -893,9 +893,22 @@ class AttentionF(torch.autograd.Function):
     """Multi-head self-attention core on the packed qkv rows [B*T, 3*D] -> [B*T, D]."""
 
     @staticmethod
-    def forward(ctx, qkv, B: int, T: int, H: int):
+    def forward(ctx, qkv, B: int, T: int, H: int, snapshot=None, site: int = 0, thr8: int = 0):
         Tp = _tp(T)
         Dh = qkv.shape[1] // (3 * H)
+        ctx.drop = None
+        if thr8:
+            # dropout on the probabilities (ringdp.ops.dropout, attention mode): the key-blocked kernels of
+            # vit_attn_drop.hip at every T; the backward regenerates the mask from (snapshot, site)
+            if Dh != 64:
+                raise NotImplementedError(f"AttentionF: attention dropout needs head dim 64, got {Dh} (the GEMM "
+                                          "path has no dropout)")
+            scale = 1.0 / math.sqrt(Dh)
+            lse, out = C.attn_drop_fwd_rows(qkv, B, T, H, scale, snapshot, site, thr8)
+            ctx.save_for_backward(qkv, lse, out)
+            ctx.cfg = (B, T, H, Tp, scale)
+            ctx.drop = (snapshot, site, thr8)
+            return out
         if Dh == 64 and (Tp <= 256 or _ATTN_RECOMPUTE) and not _ATTN_UNFUSED and not _ATTN_BWD_GEMMS:
             # fused kernels straight on the projection rows: no head-major split / merge passes.  Tp > 256 runs
             # the key-blocked kernels (log-sum-exp only), whose backward takes D = rowsum(dO * O) from `out`
@@ -927,6 +940,18 @@ class AttentionF(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
+        if ctx.drop is not None:
+            qkv, lse, out = ctx.saved_tensors
+            B, T, H, Tp, scale = ctx.cfg
+            part = None
+            if not _FP8["on"] or (_FP8["mx"] and _MX_LN_BWD_FUSED):  # column sums for the qkv bias, as below
+                part = torch.empty(C.attn_colsum_rows(B, T, True), qkv.shape[1], device=qkv.device,
+                                   dtype=torch.float32)
+            dqkv = C.attn_drop_bwd_rows(dout.contiguous(), qkv, lse, out, B, T, H, scale, *ctx.drop, part)
+            if part is not None:
+                dqkv._ringdp_colsum_part = part
+                _mx_stamp(dqkv)
+            return dqkv, None, None, None, None, None, None
         if ctx.rows:
             qkv, p, *rest = ctx.saved_tensors
             out = rest[0] if rest else None  # saved for Tp > 256 only
@@ -939,8 +964,9 @@ class AttentionF(torch.autograd.Function):
                 dqkv = C.attn_bwd_rows(dout.contiguous(), qkv, p, B, T, H, scale, part, out)
                 dqkv._ringdp_colsum_part = part
                 _mx_stamp(dqkv)  # (read by the MXFP8 linear only; the bf16 LinearF takes the partials as before)
-                return dqkv, None, None, None
-            return C.attn_bwd_rows(dout.contiguous(), qkv, p, B, T, H, scale, None, out), None, None, None
+                return dqkv, None, None, None, None, None, None
+            dqkv = C.attn_bwd_rows(dout.contiguous(), qkv, p, B, T, H, scale, None, out)
+            return dqkv, None, None, None, None, None, None
         q, k, v, p = ctx.saved_tensors
         B, T, H, Tp, scale = ctx.cfg
         BH, _, Dh = q.shape
@@ -948,7 +974,7 @@ class AttentionF(torch.autograd.Function):
         if Dh == 64 and Tp <= 256 and not _ATTN_UNFUSED and not _ATTN_BWD_GEMMS:
             # two fused kernels: query side (dS in registers, dQ) and key side (dK, dV), written
             # straight into the qkv gradient rows
-            return C.attn_bwd(do, q, k, v, p, B, T, H, scale), None, None, None
+            return C.attn_bwd(do, q, k, v, p, B, T, H, scale), None, None, None, None, None, None
         # dP = dO V^T (fp32) -> dS = scale * P * (dP - rowsum(dP * P))
         if Dh == 64 and Tp <= 256 and not _ATTN_UNFUSED:
             ds = C.attn_bwd_ds(do, v, p, scale)  # dP stays in registers
@@ -960,7 +986,7 @@ class AttentionF(torch.autograd.Function):
         dk = C.gemm(ds, q, Tp, Dh, Tp, Tp, Dh, True, True, BH, Tp * Tp, Tp * Dh, True)
         dv = C.gemm(p, do, Tp, Dh, Tp, Tp, Dh, True, True, BH, Tp * Tp, Tp * Dh, True)
         dqkv = C.qkv_merge(dq.view(BH, Tp, Dh), dk.view(BH, Tp, Dh), dv.view(BH, Tp, Dh), B, T)
-        return dqkv, None, None, None
+        return dqkv, None, None, None, None, None, None
 
 
 class PatchTokensF(torch.autograd.Function):
