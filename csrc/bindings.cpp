@@ -625,6 +625,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("labels"), py::arg("idx"), py::arg("rec"), py::arg("S"),
         py::arg("mean") = std::vector<double>{}, py::arg("std") = std::vector<double>{},
         py::arg("channels_last") = false, py::arg("out_dtype") = at::kFloat);
+  m.def("dwconv_fwd", &ops::dwconv_fwd,
+        "depthwise K x K conv of NHWC bf16 x with fp32 w [C, 1, K, K] (stride 1, padding K / 2, K in {3, 5, 7}, "
+        "C % 8 == 0); flip=True mirrors the kernel: the data gradient of dy",
+        py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("flip") = false);
+  m.def("dwconv_wgrad", &ops::dwconv_wgrad, "(dw [C, 1, K, K], db [C] or None) of the depthwise conv, fp32, fixed order",
+        py::arg("x"), py::arg("dy"), py::arg("K"), py::arg("need_bias") = true);
   m.def("layernorm_fwd", &ops::layernorm_fwd);
   m.def("layernorm_bwd", &ops::layernorm_bwd);
   m.def("layernorm_fwd_q8", &ops::layernorm_fwd_q8, "layernorm forward with e4m3 outputs (q, q^T) at a delayed scale");

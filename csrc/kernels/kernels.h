@@ -793,6 +793,19 @@ void resize_crop(const uint8_t* x, const int64_t* labels, const int64_t* idx, co
                  int B, int64_t N, int H, int W, int C, int S, const AugNorm& nrm, bool nhwc, bool out_bf16,
                  void* out, int64_t* yout, hipStream_t s);
 
+// ---------------------------------------------------------------- depthwise K x K convolution (dwconv.hip)
+// NHWC bf16 [N, H, W, C], stride 1, "same" padding K / 2, K in {3, 5, 7} (dwconv_ok), C % 8 == 0, 16-byte aligned
+// activations; w fp32 [C, 1, K, K], bias fp32 [C] or nullptr.  flip: the kernel mirrored in both axes (the data
+// gradient of dy).
+bool dwconv_ok(int K);
+void dwconv_fwd(const void* x, const float* w, const float* bias, void* y, int N, int H, int W, int C, int K, bool flip,
+                hipStream_t s);
+// dw [C, 1, K, K] and db [C] (or nullptr) in fp32 by two launches: per-workgroup partials, then a fixed-order sum.
+// partial: dwconv_wgrad_partial_floats(...) floats of scratch, fully written before it is read.
+int64_t dwconv_wgrad_partial_floats(int N, int H, int W, int C, int K, int num_cus);
+void dwconv_wgrad(const void* x, const void* dy, float* partial, float* dw, float* db, int N, int H, int W, int C,
+                  int K, int num_cus, hipStream_t s);
+
 // Synthetic MNIST-shaped batch (u8 images + labels) from a counter-based hash (deterministic).
 void synth_u8_images(uint8_t* x, int64_t* labels, int B, int HW, int num_classes, uint64_t seed,
                      hipStream_t s);

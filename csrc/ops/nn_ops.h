@@ -76,6 +76,13 @@ at::Tensor mix_draw(const at::Tensor& snapshot, int64_t R, int64_t H, int64_t W,
                     double cutmix_alpha, double prob, double switch_prob);
 std::tuple<at::Tensor, at::Tensor> mix_images(const at::Tensor& x, const at::Tensor& y, const at::Tensor& rec);
 
+// Depthwise K x K convolution on NHWC bf16 (dwconv_ops.cpp): stride 1, padding K / 2, K in {3, 5, 7}, C % 8 == 0,
+// w fp32 [C, 1, K, K], bias fp32 [C].  flip: the mirrored kernel, i.e. the data gradient of dy.  dwconv_wgrad:
+// (dw [C, 1, K, K], db [C] or None) in fp32, bitwise reproducible.
+at::Tensor dwconv_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias, bool flip);
+std::tuple<at::Tensor, c10::optional<at::Tensor>> dwconv_wgrad(const at::Tensor& x, const at::Tensor& dy, int64_t K,
+                                                               bool need_bias);
+
 // Random-resized-crop + bilinear resize for the device loader (resize_crop_ops.cpp).  crop_draw: int32 [R, 8] records
 // {y0, x0, h, w, flip, erase rows, erase columns, 0} from an rng_tick snapshot; scale = nullopt: the whole image.
 // resize_crop: (out [B, C, S, S] fp32 / bf16 in NCHW or channels-last memory, labels[idx]) from the uint8 dataset

@@ -5,6 +5,7 @@ import torch.nn as _nn
 
 from ..ops.dropout import dropout
 from ..ops.loss import cross_entropy
+from ..ops.nhwc import depthwise_conv2d
 from . import utils  # noqa: F401  (ringdp.nn.utils.clip_grad_norm_)
 
 
@@ -49,4 +50,20 @@ class Dropout(_nn.Module):
         return f"p={self.p}"
 
 
-__all__ = ["CrossEntropyLoss", "Dropout", "cross_entropy", "dropout"]
+class DepthwiseConv2d(_nn.Conv2d):
+    """``torch.nn.Conv2d(channels, channels, kernel_size, padding=kernel_size // 2, groups=channels)`` on
+    channels-last activations: takes and returns ``[N, H, W, C]`` (the first layer of a ConvNeXt block; parameter
+    names, shapes and initialisation are Conv2d's, so a torchvision ``block.0`` state dict loads).  GPU tensors are
+    bf16 and run ringdp's kernels (stride 1, ``kernel_size`` in {3, 5, 7}, ``channels % 8 == 0``; anything else
+    raises, there is no ATen fallback on the GPU); CPU tensors go to ATen."""
+
+    def __init__(self, channels: int, kernel_size: int, bias: bool = True):
+        super().__init__(channels, channels, kernel_size, padding=kernel_size // 2, groups=channels, bias=bias)
+
+    def forward(self, input):
+        if input.is_cuda:
+            return depthwise_conv2d(input, self.weight, self.bias)
+        return super().forward(input.permute(0, 3, 1, 2)).permute(0, 2, 3, 1)
+
+
+__all__ = ["CrossEntropyLoss", "DepthwiseConv2d", "Dropout", "cross_entropy", "depthwise_conv2d", "dropout"]

@@ -185,6 +185,33 @@ class MaxPoolNHWC(torch.autograd.Function):
         return C.maxpool2d_bwd(dy.contiguous(), arg, H, W, k, s, p), None, None, None
 
 
+class DepthwiseConv2dF(torch.autograd.Function):
+    """Depthwise K x K conv (stride 1, padding K // 2, K in {3, 5, 7}) of NHWC bf16 ``x`` with the fp32 weight
+    ``[C, 1, K, K]`` and bias ``[C]`` (csrc/kernels/dwconv.hip).  Backward: the data gradient is the same kernel on
+    ``dy`` with the mirrored weights; the weight and bias gradients come from a fixed-order two-launch reduction."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        ctx.save_for_backward(x, w)
+        return C.dwconv_fwd(x, w.detach(), None if b is None else b.detach(), False)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        need_dx, need_dw, need_db = ctx.needs_input_grad
+        dy = dy.contiguous()
+        dx = C.dwconv_fwd(dy, w.detach(), None, True) if need_dx else None
+        dw = db = None
+        if need_dw or need_db:
+            dw, db = C.dwconv_wgrad(x, dy, w.shape[-1], need_db)
+        return dx, dw if need_dw else None, db
+
+
+def depthwise_conv2d(x: torch.Tensor, weight: torch.Tensor, bias=None) -> torch.Tensor:
+    """``F.conv2d(x, weight, bias, padding=K // 2, groups=C)`` on NHWC bf16 ``[N, H, W, C]`` GPU activations."""
+    return DepthwiseConv2dF.apply(x, weight, bias)
+
+
 def _pad_rows(t: torch.Tensor, rows: int) -> torch.Tensor:
     if t.shape[0] == rows:
         return t.contiguous()
